@@ -28,11 +28,6 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-# HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share a queue serialise.
-# Four chain streams fill them: with RCCL's stream (N > 1) or the staged mode's copy streams beside them, the forward and the
-# reverse chain of the condensed schedule landed on one queue (chain phase 27 -> 48 ms per iteration).  Must be set before the
-# HIP runtime starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 # RCCL between processes shares device memory by dmabuf handles; the pool's host driver supports no other kind (without this,
 # ncclCommInitRank fails with "hipIpcGetMemHandle: invalid argument").  Set on the GPU boxes already; kept here for a bare environment.
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -552,7 +547,44 @@ def _check_block(a, folder, name, stations):
         return {"error": str(e)}
 
 
-HBM_PEAK_GBS = 8000.0          # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_SEED = 20261015
+DUMP_VARIANCE_BLOCKS = 3        # blocks whose rigorous variance matrices are sampled by --dump-outputs
+DUMP_VARIANCE_ENTRIES = 65536   # seeded packed entries taken from each of them (beside every station's 3x3 diagonal block)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(a, folder, stations):
+    """--dump-outputs DIR: what the timed AdjustNetwork() of the last step handed its caller, as float64 .npy files -- the adjusted
+    coordinates of every station, each iteration's largest correction, and the rigorous variance matrices of a fixed, seeded sample of
+    blocks (every station's 3x3 diagonal block plus seeded packed entries).  Inputs and samples depend on the arguments only, so two builds
+    can be compared file by file."""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    out = {"adjusted_coordinates": a.adjusted_coordinates(stations),
+           "iteration_corrections": np.array([a.GetIterationCorrection(i + 1) for i in range(a.CurrentIteration())], dtype=np.float64)}
+    nb = a.blockCount()
+    blocks = np.sort(rng.choice(nb, size=min(DUMP_VARIANCE_BLOCKS, nb), replace=False))
+    diag, entries = [], []
+    for b in blocks:
+        ap = a.block_variances_packed(int(b))
+        n = 3 * len(a.block_stations(int(b)))
+        col = np.arange(n, dtype=np.int64)
+        start = col * n - col * (col - 1) // 2            # packed lower, column by column: (i, j) at start[j] + i - j
+        j0 = 3 * np.arange(n // 3, dtype=np.int64)
+        diag.append(np.stack([ap[start[j0 + c] + r] for c in range(3) for r in range(3 - c)], axis=1))
+        entries.append(ap[np.sort(rng.choice(ap.size, size=min(DUMP_VARIANCE_ENTRIES, ap.size), replace=False))])
+    out["variance_blocks"] = blocks.astype(np.float64)
+    out["station_variances"] = np.concatenate(diag)                  # [stations of the sampled blocks, 6]: xx yx zx yy zy zz
+    out["variance_entries"] = np.concatenate(entries)
+    if sum(v.nbytes for v in out.values()) > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {sum(v.nbytes for v in out.values())} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(folder, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(folder, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+    print(f"[bench] outputs of the last timed step written to {folder}: {sorted(out)}", file=sys.stderr, flush=True)
+
+
+HBM_PEAK_GBS = 8000.0          # MI355X HBM3E
 HBM_KINDS = ["unpermute_kernel (completed inverse back to the block's unknown order: np^2 read + written)",
              "init_ordered + form_normals_ordered (normals formed in the elimination's order: lower triangle written once)",
              "gemv_* substitution from the kept factor (factor read twice per solve)",
@@ -840,6 +872,9 @@ def main():
                          "network keep the factors of iteration 1 and renew right-hand sides only")
     ap.add_argument("--no-refactor-leg", action="store_true", help="skip the extra step with a.reuse_factors = 0 behind `without_factor_reuse`")
     ap.add_argument("--no-gemm-events", action="store_true", help="diagnostic: no HIP events around the GEMM launches (roofline.achieved = 0)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (adjusted coordinates, iteration corrections, a seeded "
+                         "sample of the rigorous variances) to DIR/<name>.npy in float64 (--gpus 1 only)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-args", default="[]", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-role", default=None, help=argparse.SUPPRESS)
@@ -878,6 +913,10 @@ def main():
         raise SystemExit("bench.py needs an MI355X: the adjustment path has no CPU fallback")
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        raise SystemExit("--dump-outputs: only the single-GPU path (--gpus 1) writes its outputs")
     if launched and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
     # DNAGPU_BENCH_SHARE_GPU=1 (code-path checks on a box with fewer GPUs than ranks): ranks share devices, transport "local" inside the
@@ -1002,6 +1041,8 @@ def main():
     prof_f, prof_ms, prof_n = C.c_double(), C.c_double(), C.c_uint64()
     lib.dnagpu_profile_get(ctx, C.byref(prof_f), C.byref(prof_ms), C.byref(prof_n))
     lib.dnagpu_profile_enable(ctx, 0)
+    if args.dump_outputs:
+        dump_outputs(a, args.dump_outputs, stations)
 
     iters = a.CurrentIteration()
     solves = a.solve_count()

@@ -312,16 +312,6 @@ int check_info(dnagpu_ctx* ctx, int chain) {
     return DNAGPU_OK;
 }
 
-// HIP serialises streams that share one of its GPU_MAX_HW_QUEUES (default 4) hardware queues; the four chain streams fill them,
-// and RCCL's or the staged mode's copy streams beside them made two chains share a queue.  Raised
-// when the library is loaded -- effective unless the process started the HIP runtime before, or set the variable itself.
-// Opt-in (DNAGPU_SET_HW_QUEUES=1): a drop-in library does not change its host's environment by itself; the host sets
-// GPU_MAX_HW_QUEUES=16 before the HIP runtime starts (bench.py and the test harness do).
-__attribute__((constructor)) void dnagpu_hw_queues() {
-    const char* e = getenv("DNAGPU_SET_HW_QUEUES");
-    if (e && atoi(e) != 0) setenv("GPU_MAX_HW_QUEUES", "16", 0);
-}
-
 }  // namespace
 
 extern "C" {

@@ -5,7 +5,9 @@ others over TCP (dist_comm.cpp tcp_share_unique_id); DNAGPU_DIST_TRANSPORT=share
 (dist_comm_shared.cpp) -- and rank 0 leaves the results in <folder>/result.npz.
 WORKER_DEVICE: the HIP device of this rank (default: its rank).  WORKER_EXPECT: the transport dist_info() must report (default rccl).
 WORKER_SETTINGS: JSON of extra ProjectSettings arguments.  WORKER_DIE_AFTER_S (with WORKER_DIE_RANK): that rank kills itself that long after
-PrepareAdjustment, in the middle of the adjustment -- the others must come back with an exception, not hang."""
+PrepareAdjustment, in the middle of the adjustment -- the others must come back with an exception, not hang.  (The rank also holds at its
+second agreement of the adjustment, test hook dnaadj_debug_stall_rank, so that it is still inside AdjustNetwork() when it dies however fast
+the iterations run.)"""
 import json
 import os
 import sys
@@ -15,7 +17,6 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 from dynadjust_amd import adjust  # noqa: E402
 
 
@@ -32,7 +33,9 @@ def main():
     r, w, transport = a.dist_info()
     assert (r, w, transport) == (rank, world, expect), (r, w, transport)
     if "WORKER_DIE_AFTER_S" in os.environ and rank == int(os.environ.get("WORKER_DIE_RANK", "1")):
-        threading.Thread(target=lambda: (time.sleep(float(os.environ["WORKER_DIE_AFTER_S"])), os._exit(9)), daemon=True).start()
+        die_after = float(os.environ["WORKER_DIE_AFTER_S"])
+        a.lib.dnaadj_debug_stall_rank(rank, 2, die_after + 60.0)
+        threading.Thread(target=lambda: (time.sleep(die_after), os._exit(9)), daemon=True).start()
     t0 = time.perf_counter()
     try:
         st = a.AdjustNetwork()

@@ -23,8 +23,7 @@ EXE = os.path.join(ROOT, "tests", "cpp", "wrapper_sequence")
 
 
 def _run_wrapper(folder, name, mode, mt=0, report=0):
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="16")
-    r = subprocess.run([EXE, str(folder), name, mode, str(mt), str(report)], capture_output=True, text=True, timeout=600, env=env)
+    r = subprocess.run([EXE, str(folder), name, mode, str(mt), str(report)], capture_output=True, text=True, timeout=600)
     return r
 
 

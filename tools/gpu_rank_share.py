@@ -6,7 +6,6 @@ blocks (B, one level), the variance matrices of its blocks after the last iterat
 what such a run cannot beat, not a measurement of it.
     python tools/gpu_rank_share.py [N ...]"""
 import os, sys, time, tempfile
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dynadjust_amd import adjust
 from tests import parallel_harness as parallel
