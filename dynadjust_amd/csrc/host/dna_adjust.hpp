@@ -4,6 +4,7 @@
 // networks.  Everything numerical runs on the device through the dnagpu C-ABI
 // (include/dnagpu.h); this class only schedules blocks and keeps host-side metadata.
 #pragma once
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "../../../include/dnagpu.h"
+#include "chain_plan.hpp"
 #include "dist_comm.hpp"
 #include "dnaio.hpp"
 #include "dnatypes.hpp"
@@ -356,6 +358,24 @@ private:
     bool lock_factored_ = false;                             // the plan's factors are those of this adjustment's normals
     bool lock_keeps_ = false;                                // the plan keeps its steps' factors (they fit chain_fac_budget_)
     int lock_runs_ = 0;
+    // ... planned without the device (lockstep_plan.cpp): a step names its matrices, PrepareLockstepChains makes them and the plan
+    struct lock_ref_t {
+        enum kind_t { none, red, jfwd, jrev, merged } kind = none;
+        UINT32 i = 0;                                        // block i's red / jfwd / jrev, or merged system i
+    };
+    struct lock_merged_t { UINT32 n_stn, blk; const char* what; };   // a merged system: its stations, the block and step it is made for
+    struct lock_schedule_t {
+        int runs = 0;
+        std::vector<lock_stage_t> stages;
+        chain_plan_builder steps;                            // (their matrices not set)
+        std::vector<std::array<lock_ref_t, 3>> refs;         // per step: its sources, its output
+        std::vector<UINT32> batch_slot;                      // per batch: run / DNAGPU_CHAIN_BATCH_MAX of its members
+        std::vector<lock_merged_t> merged;
+    };
+    struct lock_scheduler;
+    // nullptr and the schedule, or why lock-step chains do not apply (want: a.chain_runs)
+    static const char* ScheduleLockstepChains(const std::vector<blockMeta_t>& meta, const std::vector<block_t>& blocks,
+                                              const std::vector<std::vector<UINT32>>& stations, int want, lock_schedule_t& out);
     // ... and the kept blocks of the rigorous solves of a many-block network as data too (matrix_only steps: RigorousBatch)
     dnagpu_chain_plan* rig_plan_ = nullptr;
     std::map<std::vector<UINT32>, size_t> rig_batches_;      // a batch's members -> its batch of rig_plan_

@@ -1210,13 +1210,7 @@ void dna_adjust::RigorousBatch(int c, const std::vector<UINT32>& ks_all) {
 // then ONE launch per batch (a dnasegment-default cut: 666 blocks x 8 launches per iteration otherwise).  Made on first use for the groups at hand.
 void dna_adjust::EnsureRigorousPlan(const std::vector<std::vector<UINT32>>& groups) {
     if (!ctx_ || rig_plan_ || rig_plan_denied_ || blockCount_ < 32 || !condensed_ok_) return;
-    struct step_data_t {
-        std::vector<UINT32> pos0, con_stn;
-        std::vector<double> con_w9;
-    };
-    std::deque<step_data_t> data;
-    std::vector<dnagpu_chain_step> steps;
-    std::vector<UINT32> batch_first{0};
+    chain_plan_builder builder;
     std::map<std::vector<UINT32>, size_t> batches;
     for (const std::vector<UINT32>& g : groups) {
         if (g.size() < 2) continue;
@@ -1234,44 +1228,38 @@ void dna_adjust::EnsureRigorousPlan(const std::vector<std::vector<UINT32>>& grou
             const blockMeta_t& meta = v_blockMeta_[k];
             const int kind = meta._blockLast ? 0 : meta._blockFirst ? 1 : 2;
             const bool rev_in = !meta._blockLast && !B.c_next.empty(), fwd_in = !meta._blockFirst && !B.c_prev.empty();
-            data.emplace_back();
-            step_data_t& D = data.back();
-            D.pos0.resize(B.keep.size());
-            std::iota(D.pos0.begin(), D.pos0.end(), 0u);
+            chain_step_data d;
             auto add_con = [&](const constraint_list& cl, double sign) {
-                D.con_stn.insert(D.con_stn.end(), cl.stn.begin(), cl.stn.end());
-                for (double w : cl.w9) D.con_w9.push_back(sign * w);
+                d.con_stn.insert(d.con_stn.end(), cl.stn.begin(), cl.stn.end());
+                for (double w : cl.w9) d.con_w9.push_back(sign * w);
             };
-            dnagpu_chain_step st{};
-            st.n_stn = (UINT32)B.keep.size();
-            st.matrix_only = 1;
-            st.src[0] = {B.red, 0, D.pos0.data(), D.pos0.size()};
-            st.n_src = 1;
+            d.n_stn = (UINT32)B.keep.size();
+            d.matrix_only = 1;
+            std::vector<UINT32> all(B.keep.size());
+            std::iota(all.begin(), all.end(), 0u);
+            d.add_source(B.red, 0, all);
             // (the order of PrepareKeptBlock's additions)
             if (kind == 0) {
                 add_con(B.ccon_fwd, +1.0);
-                if (fwd_in) st.src[st.n_src++] = {blocks_[k - 1].jfwd, 1, B.c_prev.data(), B.c_prev.size()};
+                if (fwd_in) d.add_source(blocks_[k - 1].jfwd, 1, B.c_prev);
             } else {
-                if (rev_in) st.src[st.n_src++] = {B.jrev, 1, B.c_next.data(), B.c_next.size()};
+                if (rev_in) d.add_source(B.jrev, 1, B.c_next);
                 add_con(B.ccon_rev, +1.0);
                 if (kind == 2) {
-                    if (fwd_in) st.src[st.n_src++] = {blocks_[k - 1].jfwd, 1, B.c_prev.data(), B.c_prev.size()};
+                    if (fwd_in) d.add_source(blocks_[k - 1].jfwd, 1, B.c_prev);
                     add_con(B.ccon_cmb, -1.0);
                 }
             }
-            st.con_stn = D.con_stn.data();
-            st.con_w9 = D.con_w9.data();
-            st.n_con = D.con_stn.size();
-            steps.push_back(st);
+            builder.add_step(std::move(d));
         }
-        batches[g] = batch_first.size() - 1;
-        batch_first.push_back((UINT32)steps.size());
+        batches[g] = builder.batches();
+        builder.close_batch();
     }
-    if (steps.empty()) {
+    if (!builder.steps()) {
         rig_plan_denied_ = true;
         return;
     }
-    const int rc = dnagpu_chain_plan_create(ctx_, steps.size(), steps.data(), batch_first.size() - 1, batch_first.data(), 1.0e18, &rig_plan_);
+    const int rc = builder.create(ctx_, 1.0e18, &rig_plan_);
     if (rc != DNAGPU_OK) {
         rig_plan_ = nullptr;
         rig_plan_denied_ = true;
@@ -1845,537 +1833,51 @@ void dna_adjust::FreeLockstepChains() {
     lock_runs_ = 0;
 }
 
+// the schedule (ScheduleLockstepChains, lockstep_plan.cpp) made on the device: its merged systems, then the plan of its steps
 void dna_adjust::PrepareLockstepChains() {
     FreeLockstepChains();
-    const UINT32 B = blockCount_;
     const int want = projectSettings_.a.chain_runs;
-    if (!ctx_ || want == 0 || want == 1 || !condensed_ok_ || !CondensedSchedule() || DistWorld() > 1 || ReuseRequested() || !dnagpu_info_carry(ctx_)) return;
-    // the contiguous networks of the project (dnaadjust.cpp:10449-10474: a block whose junction list is empty ends one; an isolated block
-    // is a network of its own without a chain step): their chains are independent of each other and advance together like the runs of one
-    struct net_t { UINT32 s, e; int runs; };
-    std::vector<net_t> nets;
-    std::vector<UINT32> net_s(B, 0), net_e(B, 0);
-    UINT32 chained = 0;
-    for (UINT32 k = 0; k < B;) {
-        const blockMeta_t& m = v_blockMeta_[k];
-        if (m._blockIsolated) {
-            ++k;
-            continue;
-        }
-        if (!m._blockFirst) return;
-        UINT32 e = k;
-        while (!v_blockMeta_[e]._blockLast) {
-            ++e;
-            if (e >= B || v_blockMeta_[e]._blockIsolated || v_blockMeta_[e]._blockFirst) return;
-        }
-        if (e > k) {
-            nets.push_back({k, e, 1});
-            chained += e - k + 1;
-            for (UINT32 q = k; q <= e; ++q) {
-                net_s[q] = k;
-                net_e[q] = e;
-            }
-        }
-        k = e + 1;
-    }
-    // (the runs' boundaries come from a scan -- level 2 below, 2 log2 W levels deep --, the steps inside the runs are 2 x blocks-per-run deep:
-    //  about eight blocks to a run; dnasegment150's 666 blocks: 16 / 32 / 48 / 64 / 96 / 128 / 160 runs -> 47.0 / 38.0 / 35.7 / 34.3 / 34.0 / 34.4 / 36.0 ms)
-    int W = want > 1 ? want : (chained >= 64 ? std::max<int>(16, std::min<int>(512, (int)(chained / 8))) : 1);
-    W = std::min<int>(W, (int)(chained / 3));
-    if (W < 2) return;
-    // small condensed systems, every block between two others carrying something both ways
-    for (const net_t& n : nets)
-        for (UINT32 k = n.s; k <= n.e; ++k) {
-            const block_t& Bk = blocks_[k];
-            if (Bk.keep.empty() || !Bk.red || 3 * Bk.keep.size() > 1024) return;
-            if ((k > n.s && Bk.c_prev.empty()) || (k < n.e && Bk.c_next.empty())) return;
-            if ((k < n.e && !Bk.jfwd) || (k > n.s && !blocks_[k - 1].jrev)) return;
-        }
-    // the runs: W of them dealt to the networks by their length, at least three blocks to a run
-    {
-        int total = 0;
-        for (net_t& n : nets) {
-            const UINT32 len = n.e - n.s + 1;
-            n.runs = std::max(1, std::min<int>((int)(len / 3), (int)std::lround((double)W * len / (double)chained)));
-            total += n.runs;
-        }
-        W = total;
-    }
-    auto gid = [&](UINT32 k, UINT32 keep_pos) { return v_parameterStationList_[k][blocks_[k].keep[keep_pos]]; };
-    auto position = [](const std::vector<UINT32>& sorted, UINT32 g) {
-        auto it = std::lower_bound(sorted.begin(), sorted.end(), g);
-        return (it != sorted.end() && *it == g) ? (long)(it - sorted.begin()) : -1L;
-    };
-    // the steps, in the order of the plan's batches; what their lists point at lives in `data` until the plan is made
-    struct step_data_t {
-        std::vector<UINT32> est_blk, est_idx, keep, con_stn, pos[3];
-        std::vector<double> con_w9;
-    };
-    std::deque<step_data_t> data;
-    std::vector<dnagpu_chain_step> steps;
-    std::vector<UINT32> batch_first{0};
-    std::vector<lock_stage_t> stages;
-    auto add_step = [&](step_data_t&& d, int n_src, const dnagpu_matrix* const* src, const int* src_junction, dnagpu_matrix* out, int out_junction, UINT32 n_stn) {
-        data.push_back(std::move(d));
-        step_data_t& D = data.back();
-        dnagpu_chain_step st{};
-        st.n_stn = n_stn;
-        st.est_blk = D.est_blk.empty() ? nullptr : D.est_blk.data();
-        st.est_idx = D.est_idx.empty() ? nullptr : D.est_idx.data();
-        st.n_src = n_src;
-        for (int q = 0; q < n_src; ++q) {
-            st.src[q].m = src[q];
-            st.src[q].junction = src_junction[q];
-            st.src[q].pos = D.pos[q].data();
-            st.src[q].k = D.pos[q].size();
-        }
-        st.con_stn = D.con_stn.data();
-        st.con_w9 = D.con_w9.data();
-        st.n_con = D.con_stn.size();
-        st.keep = D.keep.data();
-        st.n_keep = D.keep.size();
-        st.out = out;
-        st.out_junction = out_junction;
-        steps.push_back(st);
-        const double n = 3.0 * n_stn, nj = 3.0 * (double)D.keep.size(), ni = n - nj;
-        return ni * ni * ni / 3.0 + ni * ni * nj + ni * nj * nj;
-    };
-    // a group = one step of every run that has it, in batches of DNAGPU_CHAIN_BATCH_MAX
-    // (a run stays in the same batch slot -- run / DNAGPU_CHAIN_BATCH_MAX -- through all groups: a slot's batches follow each other on one chain)
-    struct pending_t { std::function<double()> make; bool block_step; int run; double ref_flops; };
-    std::vector<UINT32> batch_slot;
-    auto close_group = [&](lock_lane_t& lane, std::vector<pending_t>& members) {
-        if (members.empty()) return;
-        lock_group_t g;
-        g.lo = (UINT32)batch_first.size() - 1;
-        double fl = 0.0, ref = 0.0;
-        UINT32 nblk = 0;
-        for (size_t i = 0; i < members.size(); ++i) {
-            fl += members[i].make();
-            ref += members[i].ref_flops;
-            nblk += members[i].block_step ? 1u : 0u;
-            const int slot = members[i].run / DNAGPU_CHAIN_BATCH_MAX;
-            if (i + 1 == members.size() || members[i + 1].run / DNAGPU_CHAIN_BATCH_MAX != slot) {
-                batch_first.push_back((UINT32)steps.size());
-                batch_slot.push_back((UINT32)slot);
-            }
-        }
-        g.hi = (UINT32)batch_first.size() - 1;
-        lane.groups.push_back(g);
-        lane.flops.push_back(fl);
-        lane.ref_flops.push_back(ref);
-        lane.block_steps.push_back(nblk);
-        members.clear();
-    };
-    struct run_t {
-        UINT32 a, b, s, e;                   // its blocks; its network's blocks
-        int net, index, of;                  // its network; its place among that network's runs
-        std::vector<UINT32> stations, posL, posR, est_blk, est_idx, sys_pos;
-        constraint_list con_fwd, con_rev;
-        std::vector<UINT32> prev;            // stations of the running merged system
-        const dnagpu_matrix* prev_m = nullptr;
-        const dnagpu_matrix* S = nullptr;    // the run's system: the last merge's output (or the one block's condensed system)
-    };
-    std::vector<run_t> runs((size_t)W);
+    if (want == 0 || want == 1) return;
+    const char* why = !ctx_ ? "no device context" : !CondensedSchedule() ? "not the condensed schedule" : DistWorld() > 1 ? "more than one rank"
+                      : ReuseRequested() ? "a.reuse_inverses" : !dnagpu_info_carry(ctx_) ? "no info carry" : nullptr;
+    lock_schedule_t plan;
+    std::string failure;
     try {
-        {
-            int r = 0;
-            for (size_t q = 0; q < nets.size(); ++q) {
-                const UINT32 len = nets[q].e - nets[q].s + 1;
-                for (int i = 0; i < nets[q].runs; ++i, ++r) {
-                    run_t& g = runs[r];
-                    g.s = nets[q].s;
-                    g.e = nets[q].e;
-                    g.net = (int)q;
-                    g.index = i;
-                    g.of = nets[q].runs;
-                    g.a = g.s + (UINT32)((uint64_t)i * len / (uint64_t)nets[q].runs);
-                    g.b = g.s + (UINT32)((uint64_t)(i + 1) * len / (uint64_t)nets[q].runs) - 1;
-                }
-            }
+        if (!why) why = ScheduleLockstepChains(v_blockMeta_, blocks_, v_parameterStationList_, want, plan);
+        for (size_t i = 0; !why && i < plan.merged.size(); ++i) {
+            lock_mats_.push_back(nullptr);
+            NewMatrix(plan.merged[i].n_stn * 3, &lock_mats_.back(), plan.merged[i].blk, plan.merged[i].what);
         }
-        for (int r = 0; r < W; ++r) {
-            run_t& g = runs[r];
-            const block_t& A = blocks_[g.a];
-            const block_t& Z = blocks_[g.b];
-            std::vector<UINT32> L, R;
-            if (g.a > g.s)
-                for (UINT32 p : A.c_prev) L.push_back(gid(g.a, p));
-            if (g.b < g.e)
-                for (UINT32 p : Z.c_next) R.push_back(gid(g.b, p));
-            g.stations = L;
-            g.stations.insert(g.stations.end(), R.begin(), R.end());
-            std::sort(g.stations.begin(), g.stations.end());
-            g.stations.erase(std::unique(g.stations.begin(), g.stations.end()), g.stations.end());
-            for (UINT32 s : L) g.posL.push_back((UINT32)position(g.stations, s));
-            for (UINT32 s : R) g.posR.push_back((UINT32)position(g.stations, s));
-            std::set<UINT32> inL(L.begin(), L.end());
-            for (UINT32 s : g.stations) {
-                const UINT32 k = inL.count(s) ? g.a : g.b;
-                g.est_blk.push_back(k);
-                g.est_idx.push_back(LocalIndex(k, s));
+        for (size_t s = 0; !why && s < plan.refs.size(); ++s) {
+            chain_step_data& d = plan.steps.step(s);
+            dnagpu_matrix* m[3];
+            for (int q = 0; q < 3; ++q) {
+                const lock_ref_t& r = plan.refs[s][q];
+                m[q] = r.kind == lock_ref_t::red ? blocks_[r.i].red : r.kind == lock_ref_t::jfwd ? blocks_[r.i].jfwd
+                     : r.kind == lock_ref_t::jrev ? blocks_[r.i].jrev : r.kind == lock_ref_t::merged ? lock_mats_[r.i] : nullptr;
             }
-            for (UINT32 k = g.a; k <= g.b; ++k) {
-                auto pick = [&](const constraint_list& src, constraint_list& dst) {
-                    for (size_t i = 0; i < src.stn.size(); ++i) {
-                        const long q = position(g.stations, gid(k, src.stn[i]));
-                        if (q < 0) continue;
-                        dst.stn.push_back((UINT32)q);
-                        dst.w9.insert(dst.w9.end(), src.w9.begin() + 9 * i, src.w9.begin() + 9 * i + 9);
-                    }
-                };
-                pick(blocks_[k].ccon_fwd, g.con_fwd);
-                pick(blocks_[k].ccon_rev, g.con_rev);
-            }
-            g.prev.clear();
-            for (UINT32 p = 0; p < A.keep.size(); ++p) g.prev.push_back(gid(g.a, p));
-            g.prev_m = A.red;
-            if (g.a == g.b) {
-                g.S = A.red;
-                for (UINT32 s : g.prev) {
-                    const long q = position(g.stations, s);
-                    if (q < 0) return;
-                    g.sys_pos.push_back((UINT32)q);
-                }
-            }
+            std::copy(m, m + d.n_src, d.src);
+            d.out = m[2];
+            if (!m[0] || !m[d.n_src - 1] || !m[2]) why = "a step without its matrix";
         }
-        // level 1: the runs merged to their end stations, merge j of every run together
-        stages.emplace_back();
-        stages.back().lanes.emplace_back();
-        UINT32 longest = 0;
-        for (const run_t& g : runs) longest = std::max(longest, g.b - g.a);
-        bool bad = false;
-        for (UINT32 j = 1; j <= longest; ++j) {
-            std::vector<pending_t> members;
-            for (int r = 0; r < W; ++r) {
-                run_t& g = runs[r];
-                if (g.b - g.a < j || g.of < 2) continue;       // (a network that is one run needs no run system)
-                const UINT32 k = g.a + j;
-                members.push_back({[&, r, k]() -> double {
-                    run_t& g = runs[r];
-                    step_data_t d;
-                    std::vector<UINT32> blk;
-                    for (UINT32 p = 0; p < blocks_[k].keep.size(); ++p) blk.push_back(gid(k, p));
-                    std::vector<UINT32> U = g.prev;
-                    U.insert(U.end(), blk.begin(), blk.end());
-                    std::sort(U.begin(), U.end());
-                    U.erase(std::unique(U.begin(), U.end()), U.end());
-                    for (UINT32 s : g.prev) d.pos[0].push_back((UINT32)position(U, s));
-                    for (UINT32 s : blk) d.pos[1].push_back((UINT32)position(U, s));
-                    // stations that stay: the run's first junction row and block k's junction row towards k + 1
-                    std::vector<UINT32> stay;
-                    if (g.a > g.s)
-                        for (UINT32 p : blocks_[g.a].c_prev) stay.push_back(gid(g.a, p));
-                    if (k < g.e)
-                        for (UINT32 p : blocks_[k].c_next) stay.push_back(gid(k, p));
-                    std::sort(stay.begin(), stay.end());
-                    stay.erase(std::unique(stay.begin(), stay.end()), stay.end());
-                    for (UINT32 s : stay) {
-                        const long q = position(U, s);
-                        if (q < 0) bad = true;
-                        d.keep.push_back((UINT32)std::max(0L, q));
-                    }
-                    // constraints of the stations that leave inside the run: where the forward chain adds them (first appearance)
-                    for (UINT32 kk : (k == g.a + 1 ? std::vector<UINT32>{g.a, k} : std::vector<UINT32>{k})) {
-                        const constraint_list& src = blocks_[kk].ccon_fwd;
-                        for (size_t i = 0; i < src.stn.size(); ++i) {
-                            const UINT32 s = gid(kk, src.stn[i]);
-                            if (position(g.stations, s) >= 0) continue;
-                            d.con_stn.push_back((UINT32)position(U, s));
-                            d.con_w9.insert(d.con_w9.end(), src.w9.begin() + 9 * i, src.w9.begin() + 9 * i + 9);
-                        }
-                    }
-                    dnagpu_matrix* out = nullptr;
-                    NewMatrix((UINT32)stay.size() * 3, &out, k, "PrepareAdjustment(): run merge");
-                    lock_mats_.push_back(out);
-                    const dnagpu_matrix* src[2] = {g.prev_m, blocks_[k].red};
-                    const int junction[2] = {0, 0};
-                    const double fl = add_step(std::move(d), 2, src, junction, out, 0, (UINT32)U.size());
-                    g.prev = stay;
-                    g.prev_m = out;
-                    if (k == g.b) {
-                        if (stay != g.stations) bad = true;      // (the last merge must leave exactly the run's end stations)
-                        g.S = out;
-                        g.sys_pos.resize(g.stations.size());
-                        std::iota(g.sys_pos.begin(), g.sys_pos.end(), 0u);
-                    }
-                    return fl;
-                }, false, r, 0.0});
-            }
-            close_group(stages.back().lanes[0], members);
-            if (bad) {
-                FreeLockstepChains();
-                return;
-            }
-        }
-        auto nref3 = [&](UINT32 k) {
-            const double n = 3.0 * (double)v_parameterStationList_[k].size();
-            return n * n * n;
-        };
-        // level 2: the junction matrices at the runs' boundaries -- forward (everything left of a boundary condensed onto it) and reverse -- as a
-        // SCAN over the runs of a network instead of two chains of W - 1 steps each (round 6).  The runs' systems are the leaves of a binary
-        // tree; going up, the two halves of a span are merged to the span's end stations (its first run's junction row towards the run
-        // before, its last run's towards the run after: the step of level 1, on two systems); going down, a node hands the junction matrix
-        // at its middle boundary to both sides -- forward from its left half and the forward matrix at its own left end, reverse from its
-        // right half and the reverse matrix at its right end.  2 log2 W levels instead of W - 1, every level's steps of all networks in
-        // merged launches; the same additions, associated differently: results agree with the step-by-step chains to rounding.
-        // A station's constraint weights go in where the station leaves (a merge) or where the chain in question meets it first (a
-        // boundary step: the stations that stay, unless the matrix carried in has them already) -- once per direction, as in
-        // AddConstraintStationstoNormalsForward / ...Reverse (ADJ:1884-1958).
-        struct span_t {
-            int i = 0, j = 0;                       // its runs (indices into `runs`)
-            int left = -1, right = -1, height = 0, depth = 0;
-            std::vector<UINT32> stations;           // L(i) u R(j), global ids, ascending
-            std::vector<UINT32> sys;                // global ids in the order of S's stations (set when S is)
-            const dnagpu_matrix* S = nullptr;
-        };
-        std::vector<span_t> spans;
-        std::vector<int> roots;
-        std::map<UINT32, std::array<double, 9>> end_con;       // constraint weights of the runs' end stations, by global id
-        auto run_L = [&](int r) {
-            std::vector<UINT32> v;
-            for (UINT32 q : runs[r].posL) v.push_back(runs[r].stations[q]);
-            return v;
-        };
-        auto run_R = [&](int r) {
-            std::vector<UINT32> v;
-            for (UINT32 q : runs[r].posR) v.push_back(runs[r].stations[q]);
-            return v;
-        };
-        for (const run_t& g : runs)
-            for (const constraint_list* cl : {&g.con_fwd, &g.con_rev})
-                for (size_t q = 0; q < cl->stn.size(); ++q) {
-                    std::array<double, 9> w;
-                    std::copy(cl->w9.begin() + 9 * q, cl->w9.begin() + 9 * q + 9, w.begin());
-                    end_con[g.stations[cl->stn[q]]] = w;
-                }
-        std::function<int(int, int, int)> build = [&](int i, int j, int depth) -> int {
-            span_t sp;
-            sp.i = i;
-            sp.j = j;
-            sp.depth = depth;
-            sp.stations = run_L(i);
-            const std::vector<UINT32> R = run_R(j);
-            sp.stations.insert(sp.stations.end(), R.begin(), R.end());
-            std::sort(sp.stations.begin(), sp.stations.end());
-            sp.stations.erase(std::unique(sp.stations.begin(), sp.stations.end()), sp.stations.end());
-            if (i < j) {
-                const int m = i + (j - i) / 2;
-                sp.left = build(i, m, depth + 1);
-                sp.right = build(m + 1, j, depth + 1);
-                sp.height = 1 + std::max(spans[sp.left].height, spans[sp.right].height);
-            }
-            spans.push_back(std::move(sp));
-            return (int)spans.size() - 1;
-        };
-        {
-            int r0 = 0;
-            for (const net_t& n : nets) {
-                if (n.runs >= 2) roots.push_back(build(r0, r0 + n.runs - 1, 0));
-                r0 += n.runs;
-            }
-        }
-        auto leaf_system = [&](span_t& sp) {       // (a leaf's system is its run's: known once level 1's steps have been made)
-            if (sp.left >= 0 || sp.S) return;
-            const run_t& g = runs[sp.i];
-            sp.S = g.S;
-            for (UINT32 q : g.sys_pos) sp.sys.push_back(g.stations[q]);
-        };
-        auto positions = [&](const std::vector<UINT32>& sorted, const std::vector<UINT32>& ids, std::vector<UINT32>& out) {
-            for (UINT32 s : ids) {
-                const long q = position(sorted, s);
-                if (q < 0) bad = true;
-                out.push_back((UINT32)std::max(0L, q));
-            }
-        };
-        auto add_con = [&](step_data_t& d, const std::vector<UINT32>& sorted, UINT32 s) {
-            const auto it = end_con.find(s);
-            const long q = position(sorted, s);
-            if (it == end_con.end() || q < 0) {
-                bad = true;
-                return;
-            }
-            d.con_stn.push_back((UINT32)q);
-            d.con_w9.insert(d.con_w9.end(), it->second.begin(), it->second.end());
-        };
-        int top = 0, deepest = 0;
-        for (const span_t& sp : spans) {
-            top = std::max(top, sp.height);
-            deepest = std::max(deepest, sp.depth);
-        }
-        // ... going up: the spans that somebody's boundary step needs (all but the roots), lowest first.  (One lane beside an empty one:
-        // a stage of ONE lane has its batches dealt to the chains, and a merge reads what any batch of the level below has written.)
-        stages.emplace_back();
-        stages.back().lanes.resize(2);
-        for (int h = 1; h < top; ++h) {
-            std::vector<pending_t> members;
-            int idx = 0;
-            for (size_t q = 0; q < spans.size(); ++q) {
-                if (spans[q].height != h || spans[q].depth == 0) continue;
-                members.push_back({[&, q]() -> double {
-                    span_t& N = spans[q];
-                    span_t& A = spans[N.left];
-                    span_t& Bs = spans[N.right];
-                    leaf_system(A);
-                    leaf_system(Bs);
-                    step_data_t d;
-                    std::vector<UINT32> U = A.stations;
-                    U.insert(U.end(), Bs.stations.begin(), Bs.stations.end());
-                    std::sort(U.begin(), U.end());
-                    U.erase(std::unique(U.begin(), U.end()), U.end());
-                    positions(U, A.sys, d.pos[0]);
-                    positions(U, Bs.sys, d.pos[1]);
-                    positions(U, N.stations, d.keep);
-                    for (UINT32 s : U)
-                        if (position(N.stations, s) < 0) add_con(d, U, s);
-                    if (!A.S || !Bs.S) {
-                        bad = true;
-                        return 0.0;
-                    }
-                    dnagpu_matrix* out = nullptr;
-                    NewMatrix((UINT32)N.stations.size() * 3, &out, runs[N.i].a, "PrepareAdjustment(): span merge");
-                    lock_mats_.push_back(out);
-                    const dnagpu_matrix* src[2] = {A.S, Bs.S};
-                    const int junction[2] = {0, 0};
-                    const double fl = add_step(std::move(d), 2, src, junction, out, 0, (UINT32)U.size());
-                    N.S = out;
-                    N.sys = N.stations;
-                    return fl;
-                }, false, idx++, 0.0});
-            }
-            close_group(stages.back().lanes[0], members);
-            if (bad) {
-                FreeLockstepChains();
-                return;
-            }
-        }
-        // ... going down: the node's middle boundary, forward (lane 0) and reverse (lane 1)
-        stages.emplace_back();
-        stages.back().lanes.resize(2);
-        for (int dir = 0; dir < 2; ++dir)
-            for (int dep = 0; dep <= deepest; ++dep) {
-                std::vector<pending_t> members;
-                int idx = 0;
-                for (size_t q = 0; q < spans.size(); ++q) {
-                    if (spans[q].depth != dep || spans[q].left < 0) continue;
-                    const int m = spans[spans[q].left].j;         // the boundary between runs m and m + 1
-                    members.push_back({[&, q, dir, m]() -> double {
-                        span_t& N = spans[q];
-                        span_t& H = spans[dir == 0 ? N.left : N.right];      // the half the boundary's matrix is condensed from
-                        leaf_system(H);
-                        if (!H.S) {
-                            bad = true;
-                            return 0.0;
-                        }
-                        const int first = N.i - runs[N.i].index, last = first + runs[N.i].of - 1;      // the network's runs
-                        step_data_t d;
-                        positions(H.stations, H.sys, d.pos[0]);
-                        const std::vector<UINT32> Lh = run_L(H.i), Rh = run_R(H.j);
-                        const std::vector<UINT32>& in = dir == 0 ? Lh : Rh;           // where the carried matrix comes in ...
-                        const std::vector<UINT32>& outl = dir == 0 ? Rh : Lh;         // ... and what this step leaves
-                        const bool carried = dir == 0 ? H.i > first : H.j < last;
-                        std::set<UINT32> in_set;
-                        if (carried) in_set.insert(in.begin(), in.end());
-                        positions(H.stations, outl, d.keep);
-                        for (UINT32 s : outl)
-                            if (!in_set.count(s)) add_con(d, H.stations, s);
-                        const std::set<UINT32> from_left(Lh.begin(), Lh.end());
-                        for (UINT32 s : H.stations) {
-                            const UINT32 k = from_left.count(s) ? runs[H.i].a : runs[H.j].b;
-                            d.est_blk.push_back(k);
-                            d.est_idx.push_back(LocalIndex(k, s));
-                        }
-                        const dnagpu_matrix* src[2] = {H.S, nullptr};
-                        const int junction[2] = {0, 1};
-                        int n_src = 1;
-                        if (carried) {
-                            positions(H.stations, in, d.pos[1]);
-                            src[1] = dir == 0 ? blocks_[runs[H.i].a - 1].jfwd : blocks_[runs[H.j].b].jrev;
-                            n_src = 2;
-                        }
-                        dnagpu_matrix* out = dir == 0 ? blocks_[runs[m].b].jfwd : blocks_[runs[m + 1].a - 1].jrev;
-                        return add_step(std::move(d), n_src, src, junction, out, 1, (UINT32)H.stations.size());
-                    }, true, idx++, nref3(dir == 0 ? runs[m].b : runs[m + 1].a)});   // (what the chain's step on that block leaves: counted as that step)
-                }
-                close_group(stages.back().lanes[(size_t)dir], members);
-                if (bad) {
-                    FreeLockstepChains();
-                    return;
-                }
-            }
-        // level 3: both chains inside every run, from the boundary values of level 2 (CondensedForwardBlock / CondensedReverseBlock as data)
-        // (a lane per direction and batch slot: the slots of a direction are independent of each other and go to chains of their own)
-        const int slots = (W + DNAGPU_CHAIN_BATCH_MAX - 1) / DNAGPU_CHAIN_BATCH_MAX;
-        stages.emplace_back();
-        stages.back().lanes.resize((size_t)(2 * slots));
-        auto block_step = [&](UINT32 k, int dir) -> double {
-            const block_t& Bk = blocks_[k];
-            step_data_t d;
-            d.est_blk.assign(Bk.keep.size(), k);
-            d.est_idx = Bk.keep;
-            d.pos[0].resize(Bk.keep.size());
-            std::iota(d.pos[0].begin(), d.pos[0].end(), 0u);
-            const constraint_list& con = dir == 0 ? Bk.ccon_fwd : Bk.ccon_rev;
-            d.con_stn = con.stn;
-            d.con_w9 = con.w9;
-            const dnagpu_matrix* src[2] = {Bk.red, nullptr};
-            const int junction[2] = {0, 1};
-            int n_src = 1;
-            dnagpu_matrix* out;
-            if (dir == 0) {
-                d.keep = Bk.c_next;
-                if (k > net_s[k]) {
-                    d.pos[1] = Bk.c_prev;
-                    src[1] = blocks_[k - 1].jfwd;
-                    n_src = 2;
-                }
-                out = Bk.jfwd;
-            } else {
-                d.keep = Bk.c_prev;
-                if (k < net_e[k]) {
-                    d.pos[1] = Bk.c_next;
-                    src[1] = Bk.jrev;
-                    n_src = 2;
-                }
-                out = blocks_[k - 1].jrev;
-            }
-            return add_step(std::move(d), n_src, src, junction, out, 1, (UINT32)Bk.keep.size());
-        };
-        for (int slot = 0; slot < slots; ++slot) {
-            const int r_lo = slot * DNAGPU_CHAIN_BATCH_MAX, r_hi = std::min(W, r_lo + DNAGPU_CHAIN_BATCH_MAX);
-            for (UINT32 j = 0; j <= longest; ++j) {
-                std::vector<pending_t> members;
-                for (int r = r_lo; r < r_hi; ++r) {
-                    const run_t& g = runs[r];
-                    if (g.a + j + 1 > g.b) continue;
-                    const UINT32 k = g.a + j;
-                    members.push_back({[&, k]() -> double { return block_step(k, 0); }, true, r, nref3(k)});
-                }
-                close_group(stages.back().lanes[(size_t)(2 * slot)], members);
-            }
-            for (UINT32 j = 0; j <= longest; ++j) {
-                std::vector<pending_t> members;
-                for (int r = r_lo; r < r_hi; ++r) {
-                    const run_t& g = runs[r];
-                    if (g.b < g.a + 1 + j) continue;
-                    const UINT32 k = g.b - j;
-                    members.push_back({[&, k]() -> double { return block_step(k, 1); }, true, r, nref3(k)});
-                }
-                close_group(stages.back().lanes[(size_t)(2 * slot + 1)], members);
-            }
-        }
-    } catch (...) {
-        FreeLockstepChains();      // (no room for the merged systems: the chains go step by step)
+    } catch (const std::exception& e) {
+        failure = e.what();
+        failure.resize(std::min(failure.size(), failure.find('\n')));      // (a device error: its first line)
+        why = failure.c_str();
+    }
+    if (why) {      // (the chains go step by step)
+        FreeLockstepChains();
+        if (getenv("DNAGPU_PHASE_TIMES")) fprintf(stderr, "[phase] chain plan: not made (%s)\n", why);
         return;
     }
     // the steps' factors are kept (a.reuse_factors: right-hand sides only from iteration 2 on) while they fit what PrepareCondensedBlocks set
     // aside for chain steps' factors; beyond that the plan keeps none and every iteration eliminates again -- in lock step all the same
     // (a network of many small blocks leaves most of the memory unused: its plan may take up to half of what the batch workspaces were left)
     const double budget = FactorReuse() ? std::max(chain_fac_budget_, std::min(0.5 * batch_budget_, 96.0e9)) : 0.0;
-    const int rc = dnagpu_chain_plan_create(ctx_, steps.size(), steps.data(), batch_first.size() - 1, batch_first.data(), budget, &lock_plan_);
+    const int rc = plan.steps.create(ctx_, budget, &lock_plan_);
     if (getenv("DNAGPU_PHASE_TIMES"))
-        fprintf(stderr, "[phase] chain plan: %d runs, %zu steps in %zu batches: %s (budget for kept factors %.2f GB)\n", W, steps.size(), batch_first.size() - 1,
-                rc == DNAGPU_OK ? "made" : "not made", budget / 1.0e9);
+        fprintf(stderr, "[phase] chain plan: %d runs, %zu steps in %zu batches: %s (budget for kept factors %.2f GB)\n", plan.runs, plan.steps.steps(),
+                plan.steps.batches(), rc == DNAGPU_OK ? "made" : "not made", budget / 1.0e9);
     if (rc != DNAGPU_OK) {
         lock_plan_ = nullptr;
         FreeLockstepChains();
@@ -2392,9 +1894,9 @@ void dna_adjust::PrepareLockstepChains() {
         batch_budget_ = std::max(0.0, batch_budget_ - (bytes - own));
         batch_limit_ = (int)std::max(0.0, std::min(1.0e6, batch_unit_ > 0.0 ? batch_budget_ / batch_unit_ : 0.0));
     }
-    lock_stages_ = std::move(stages);
-    lock_batch_slot_ = std::move(batch_slot);
-    lock_runs_ = W;
+    lock_stages_ = std::move(plan.stages);
+    lock_batch_slot_ = std::move(plan.batch_slot);
+    lock_runs_ = plan.runs;
     lockstep_ok_ = true;
 }
 
