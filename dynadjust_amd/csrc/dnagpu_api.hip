@@ -97,37 +97,12 @@ int ensure_ws(dnagpu_ctx* ctx, int chain, uint32_t np) {
 }
 
 int ensure_symv(dnagpu_ctx* ctx, int chain, uint32_t np) {
-    if (ctx->symv_cap[chain] >= np) return DNAGPU_OK;
-    HIPCHK(hipStreamSynchronize(ctx->stream[chain]));
-    if (ctx->symv_part[chain]) hipFree(ctx->symv_part[chain]);
-    ctx->symv_part[chain] = nullptr;
-    ctx->symv_cap[chain] = 0;
-    HIPCHK(dnagpu::poison_malloc(&ctx->symv_part[chain], (size_t)SYMV_CHUNKS * np * sizeof(double)));
-    ctx->symv_cap[chain] = np;
-    return DNAGPU_OK;
-}
-
-int ensure_scr_u32(dnagpu_ctx* ctx, int chain, size_t count) {
-    if (ctx->scr_u32_cap[chain] >= count) return DNAGPU_OK;
-    HIPCHK(hipStreamSynchronize(ctx->stream[chain]));
-    if (ctx->scr_u32[chain]) hipFree(ctx->scr_u32[chain]);
-    ctx->scr_u32[chain] = nullptr;
-    ctx->scr_u32_cap[chain] = 0;
-    size_t cap = std::max<size_t>(count, 4096);
-    HIPCHK(dnagpu::poison_malloc(&ctx->scr_u32[chain], cap * sizeof(uint32_t)));
-    ctx->scr_u32_cap[chain] = cap;
+    HIPCHK(ctx->symv_part[chain].grow((size_t)SYMV_CHUNKS * np, 0, {ctx->stream[chain]}));
     return DNAGPU_OK;
 }
 
 int ensure_scr_f64(dnagpu_ctx* ctx, int chain, size_t count) {
-    if (ctx->scr_f64_cap[chain] >= count) return DNAGPU_OK;
-    HIPCHK(hipStreamSynchronize(ctx->stream[chain]));
-    if (ctx->scr_f64[chain]) hipFree(ctx->scr_f64[chain]);
-    ctx->scr_f64[chain] = nullptr;
-    ctx->scr_f64_cap[chain] = 0;
-    size_t cap = std::max<size_t>(count, 4096);
-    HIPCHK(dnagpu::poison_malloc(&ctx->scr_f64[chain], cap * sizeof(double)));
-    ctx->scr_f64_cap[chain] = cap;
+    HIPCHK(ctx->scr_f64[chain].grow(count, 4096, {ctx->stream[chain]}));
     return DNAGPU_OK;
 }
 
@@ -167,28 +142,34 @@ struct HbmTimed {
     }
 };
 
-void free_index_cache(dnagpu_ctx* ctx, int chain) {
-    for (auto& kv : ctx->idx_cache[chain])
-        if (kv.second.dev) hipFree(kv.second.dev);
-    ctx->idx_cache[chain].clear();
-    for (auto& kv : ctx->val_cache[chain])
-        if (kv.second.dev) hipFree(kv.second.dev);
-    ctx->val_cache[chain].clear();
-}
-
-// upload a small host array to the chain's staging buffer (stream ordered).  Lists of 64 entries or more are kept (ctx.h IndexList):
+// upload a small host array to the chain's staging buffer (stream ordered).  Lists that come back are kept (ctx.h CachedList):
 // the chain steps and rigorous solves of the condensed schedule send the same station lists in every iteration, and the upload's
 // stream synchronisation -- 4 - 5 per chain step of ~1.8 ms -- was a tenth of the chain phase
-int stage_u32(dnagpu_ctx* ctx, int chain, const uint32_t* host, size_t count, uint32_t** dev) {
-    // (round 5: lists from 4 entries on -- a dnasegment-default cut has junction lists of a few dozen stations, and every list that misses
-    //  the cache costs a stream synchronisation in every chain step of every iteration)
-    if (count >= 1) {      // (every list: a one-station list of constraints through the staging buffer kept its whole batch off the merged launches)
-        uint64_t h = 1469598103934665603ull ^ (uint64_t)count;
-        for (size_t i = 0; i < count; ++i) h = (h ^ host[i]) * 1099511628211ull;
-        auto& cache = ctx->idx_cache[chain];
+// (round 5: index lists from 4 entries on -- a dnasegment-default cut has junction lists of a few dozen stations, and every list that misses
+//  the cache costs a stream synchronisation in every chain step of every iteration; then every list: a one-station list of constraints
+//  through the staging buffer kept its whole batch off the merged launches.  The constraint weights are kept by content like the index
+//  lists -- those of a chain step are the same in every iteration, and the upload's stream synchronisation stood in every step of a chain
+//  that otherwise waits for nothing)
+bool cacheable(const uint32_t*, size_t count) { return count >= 1; }
+bool cacheable(const double*, size_t count) { return count >= 9 && count <= 9 * 4096; }
+auto& list_cache(dnagpu_ctx* ctx, int chain, const uint32_t*) { return ctx->idx_cache[chain]; }
+auto& list_cache(dnagpu_ctx* ctx, int chain, const double*) { return ctx->val_cache[chain]; }
+DevBuf<uint32_t>& scratch(dnagpu_ctx* ctx, int chain, const uint32_t*) { return ctx->scr_u32[chain]; }
+DevBuf<double>& scratch(dnagpu_ctx* ctx, int chain, const double*) { return ctx->scr_f64[chain]; }
+
+template <class T>
+int stage(dnagpu_ctx* ctx, int chain, const T* host, size_t count, T** dev) {
+    if (cacheable(host, count)) {
+        uint64_t h = 1469598103934665603ull ^ (uint64_t)count;       // (FNV-1a over the elements' bits)
+        for (size_t i = 0; i < count; ++i) {
+            std::conditional_t<sizeof(T) == 8, uint64_t, uint32_t> bits;
+            memcpy(&bits, host + i, sizeof(bits));
+            h = (h ^ bits) * 1099511628211ull;
+        }
+        auto& cache = list_cache(ctx, chain, host);
         auto range = cache.equal_range(h);
         for (auto it = range.first; it != range.second; ++it)
-            if (it->second.host.size() == count && !memcmp(it->second.host.data(), host, count * sizeof(uint32_t))) {
+            if (it->second.host.size() == count && !memcmp(it->second.host.data(), host, count * sizeof(T))) {
                 *dev = it->second.dev;
                 return DNAGPU_OK;
             }
@@ -196,92 +177,37 @@ int stage_u32(dnagpu_ctx* ctx, int chain, const uint32_t* host, size_t count, ui
         // one chain), and a full cache is NOT flushed -- a flush in every iteration would cost more than the staging buffer it replaced --
         // the list at hand simply takes the staging buffer below
         const size_t cap = std::max<size_t>(512, 24 * ctx->blocks.size());
-        uint32_t* d = nullptr;
-        hipError_t e = cache.size() >= cap ? hipErrorOutOfMemory : dnagpu::poison_malloc(&d, count * sizeof(uint32_t));
+        dnagpu_ctx::CachedList<T> l;
+        hipError_t e = cache.size() >= cap ? hipErrorOutOfMemory : l.dev.alloc(count);
+        if (e == hipSuccess) e = hipMemcpy(l.dev, host, count * sizeof(T), hipMemcpyHostToDevice);
         if (e == hipSuccess) {
-            e = hipMemcpy(d, host, count * sizeof(uint32_t), hipMemcpyHostToDevice);
-            if (e == hipSuccess) {
-                dnagpu_ctx::IndexList l;
-                l.host.assign(host, host + count);
-                l.dev = d;
-                cache.emplace(h, std::move(l));
-                *dev = d;
-                return DNAGPU_OK;
-            }
-            hipFree(d);
+            l.host.assign(host, host + count);
+            *dev = l.dev;
+            cache.emplace(h, std::move(l));
+            return DNAGPU_OK;
         }
         (void)hipGetLastError();        // (no room for a copy of its own: the staging buffer as before)
     }
-    int rc = ensure_scr_u32(ctx, chain, count);
-    if (rc) return rc;
+    DevBuf<T>& scr = scratch(ctx, chain, host);
+    HIPCHK(scr.grow(count, 4096, {ctx->stream[chain]}));
     // the previous user of the staging buffer may still be running: the copy is
     // stream ordered behind it, but the host source must stay valid -> sync copy
-    HIPCHK(hipMemcpyAsync(ctx->scr_u32[chain], host, count * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream[chain]));
+    HIPCHK(hipMemcpyAsync(scr, host, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream[chain]));
     HIPCHK(hipStreamSynchronize(ctx->stream[chain]));
-    *dev = ctx->scr_u32[chain];
+    *dev = scr;
     return DNAGPU_OK;
 }
 
-int stage_f64(dnagpu_ctx* ctx, int chain, const double* host, size_t count, double** dev) {
-    // (round 5: kept by content like the index lists -- the constraint weights of a chain step are the same in every iteration, and the
-    //  upload's stream synchronisation stood in every step of a chain that otherwise waits for nothing)
-    if (count >= 9 && count <= 9 * 4096) {
-        uint64_t h = 1469598103934665603ull ^ (uint64_t)count;
-        for (size_t i = 0; i < count; ++i) {
-            uint64_t bits;
-            memcpy(&bits, host + i, sizeof(bits));
-            h = (h ^ bits) * 1099511628211ull;
-        }
-        auto& cache = ctx->val_cache[chain];
-        auto range = cache.equal_range(h);
-        for (auto it = range.first; it != range.second; ++it)
-            if (it->second.host.size() == count && !memcmp(it->second.host.data(), host, count * sizeof(double))) {
-                *dev = it->second.dev;
-                return DNAGPU_OK;
-            }
-        const size_t cap = std::max<size_t>(512, 24 * ctx->blocks.size());
-        double* d = nullptr;
-        hipError_t e = cache.size() >= cap ? hipErrorOutOfMemory : dnagpu::poison_malloc(&d, count * sizeof(double));
-        if (e == hipSuccess) {
-            e = hipMemcpy(d, host, count * sizeof(double), hipMemcpyHostToDevice);
-            if (e == hipSuccess) {
-                dnagpu_ctx::ValueList l;
-                l.host.assign(host, host + count);
-                l.dev = d;
-                cache.emplace(h, std::move(l));
-                *dev = d;
-                return DNAGPU_OK;
-            }
-            hipFree(d);
-        }
-        (void)hipGetLastError();
-    }
-    int rc = ensure_scr_f64(ctx, chain, count);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->scr_f64[chain], host, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream[chain]));
-    HIPCHK(hipStreamSynchronize(ctx->stream[chain]));
-    *dev = ctx->scr_f64[chain];
-    return DNAGPU_OK;
+// a block's index list on the device (at least one element, so that an empty list is a valid pointer too)
+hipError_t upload_list(DevBuf<uint32_t>& dev, const std::vector<uint32_t>& v) {
+    hipError_t e = dev.alloc(std::max<size_t>(v.size(), 1));
+    if (e == hipSuccess && !v.empty()) e = hipMemcpy(dev, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    return e;
 }
 
 Block* find_block(dnagpu_ctx* ctx, uint32_t blk) {
     auto it = ctx->blocks.find(blk);
     return it == ctx->blocks.end() ? nullptr : &it->second;
-}
-
-void free_block(Block& b) {
-    // (dnagpu_block_create's arrays -- stations, vectors per chain, baselines -- are one arena)
-    if (b.arena) hipFree(b.arena);
-    for (int c = 0; c < DNAGPU_NUM_CHAINS; ++c)
-        for (void* p : {(void*)b.tb[c], (void*)b.trow[c], b.wb_own ? (void*)b.wb[c] : nullptr})
-            if (p) hipFree(p);
-    void* ptrs[] = {b.Wblk, b.pair_row, b.pair_col, b.pair_off, b.pair_ent, b.inc_off, b.inc,
-                    b.t_type, b.t_stn, b.t_blk0, b.t_vec0, b.t_val, b.t_pre, b.t_var, b.t_ih, b.t_th, b.s_llh, b.s_geoid, b.s_defl,
-                    b.ds_a, b.ds_b, b.ds_pq, b.ds_w, b.ds_row0, b.ds_k, b.ds_woff, b.ds_wts, b.osc_gidx, b.osc_visit, b.corr_keep, b.schur_idx[0], b.schur_idx[1], b.schur_map[0], b.schur_map[1], b.schur_spos[0], b.schur_spos[1]};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    for (void* p : b.retired) hipFree(p);
-    b = Block();
 }
 
 double* station_vec(Block& b, int which, int chain) {
@@ -338,14 +264,13 @@ int dnagpu_create(int device, dnagpu_ctx** out) {
     for (int c = 0; c < DNAGPU_NUM_CHAINS; ++c) {
         if (hipStreamCreateWithFlags(&ctx->stream[c], hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&ctx->ev[c], hipEventDisableTiming) != hipSuccess ||
-            hipHostMalloc(&ctx->red_val_host[c], sizeof(double)) != hipSuccess ||
-            hipHostMalloc(&ctx->red_idx_host[c], sizeof(uint32_t)) != hipSuccess) {
+            ctx->red_val_host[c].alloc(1) != hipSuccess || ctx->red_idx_host[c].alloc(1) != hipSuccess) {
             dnagpu_destroy(ctx);
             return DNAGPU_EHIP;
         }
         ctx->ws[c].stream = ctx->stream[c];
     }
-    if (dnagpu::poison_malloc(&ctx->bad_dev, sizeof(int)) != hipSuccess) {
+    if (ctx->bad_dev.alloc(1) != hipSuccess) {
         dnagpu_destroy(ctx);
         return DNAGPU_ENOMEM;
     }
@@ -357,28 +282,15 @@ void dnagpu_destroy(dnagpu_ctx* ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
     hipDeviceSynchronize();
-    for (auto& kv : ctx->blocks) free_block(kv.second);
     ctx->blocks.clear();
     for (int c = 0; c < DNAGPU_NUM_CHAINS; ++c) {
         inv_workspace_free(ctx->ws[c]);
-        if (ctx->symv_part[c]) hipFree(ctx->symv_part[c]);
-        if (ctx->scr_u32[c]) hipFree(ctx->scr_u32[c]);
-        free_index_cache(ctx, c);
-        if (ctx->scr_f64[c]) hipFree(ctx->scr_f64[c]);
-        if (ctx->red_val_host[c]) hipHostFree(ctx->red_val_host[c]);
-        if (ctx->red_idx_host[c]) hipHostFree(ctx->red_idx_host[c]);
         if (ctx->ev[c]) hipEventDestroy(ctx->ev[c]);
         if (ctx->stream[c]) hipStreamDestroy(ctx->stream[c]);
-        if (ctx->stage_buf[c]) hipFree(ctx->stage_buf[c]);
         if (ctx->pack_done[c]) hipEventDestroy(ctx->pack_done[c]);
         if (ctx->copy_done[c]) hipEventDestroy(ctx->copy_done[c]);
         if (ctx->copy_stream[c]) hipStreamDestroy(ctx->copy_stream[c]);
     }
-    if (ctx->bad_dev) hipFree(ctx->bad_dev);
-    for (int c = 0; c < DNAGPU_NUM_CHAINS; ++c)
-        if (ctx->plan_scratch[c]) hipFree(ctx->plan_scratch[c]);
-    for (void* p : {(void*)ctx->osc_prev, (void*)ctx->osc_seen, (void*)ctx->osc_cnt, (void*)ctx->osc_flagged, ctx->osc_rows, (void*)ctx->osc_off, ctx->osc_visits})
-        if (p) hipFree(p);
     for (int c = 0; c < DNAGPU_NUM_CHAINS; ++c) {
         for (auto& r : ctx->hbm_recs[c]) {
             hipEventDestroy(r.e0);
@@ -386,7 +298,7 @@ void dnagpu_destroy(dnagpu_ctx* ctx) {
         }
         for (hipEvent_t e : ctx->hbm_free[c]) hipEventDestroy(e);
     }
-    delete ctx;
+    delete ctx;         // (the context's buffers go with it)
 }
 
 // the calling thread's own failure on this context if it has one it has not read yet, else the context's latest
@@ -618,10 +530,9 @@ int dnagpu_matrix_create(dnagpu_ctx* ctx, uint32_t n_max, dnagpu_matrix** out) {
     m->n_max = n_max;
     m->np_max = pad128(n_max);
     // one spare tile row: dnagpu_schur_carry keeps (np + 128) x np panels here
-    hipError_t e = dnagpu::poison_malloc(&m->F, ((size_t)m->np_max + 128) * m->np_max * sizeof(double));
-    if (e == hipSuccess) e = dnagpu::poison_malloc(&m->jest, (size_t)m->np_max * sizeof(double));
+    hipError_t e = m->F.alloc(((size_t)m->np_max + 128) * m->np_max);
+    if (e == hipSuccess) e = m->jest.alloc(m->np_max);
     if (e != hipSuccess) {
-        if (m->F) hipFree(m->F);
         delete m;
         return fail(ctx, e == hipErrorOutOfMemory ? DNAGPU_ENOMEM : DNAGPU_EHIP, "matrix allocation", e);
     }
@@ -637,9 +548,6 @@ void dnagpu_matrix_destroy(dnagpu_ctx* ctx, dnagpu_matrix* m) {
         hipSetDevice(ctx->device);
         hipDeviceSynchronize();
     }
-    if (m->F) hipFree(m->F);
-    if (m->jest) hipFree(m->jest);
-    if (m->jrhs) hipFree(m->jrhs);
     delete m;
 }
 
@@ -701,7 +609,7 @@ static int ensure_copy_stage(dnagpu_ctx* ctx, int chain, size_t cnt, int* rc_out
         ctx->pack_done[chain] = pd;
         ctx->copy_done[chain] = cd;
     }
-    if (ctx->stage_cap[chain] < cnt) {
+    if (ctx->stage_buf[chain].cap() < cnt) {
         hipError_t e = hipStreamSynchronize(ctx->copy_stream[chain]);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream[chain]);      // (an upload through the buffer that the chain has not consumed yet)
         if (e != hipSuccess) {
@@ -709,15 +617,10 @@ static int ensure_copy_stage(dnagpu_ctx* ctx, int chain, size_t cnt, int* rc_out
             return 0;
         }
         ctx->copy_pending[chain] = false;
-        if (ctx->stage_buf[chain]) hipFree(ctx->stage_buf[chain]);
-        ctx->stage_buf[chain] = nullptr;
-        ctx->stage_cap[chain] = 0;
-        if (dnagpu::poison_malloc(&ctx->stage_buf[chain], cnt * sizeof(double)) != hipSuccess) {
+        if (ctx->stage_buf[chain].grow(cnt, 0) != hipSuccess) {
             (void)hipGetLastError();
-            ctx->stage_buf[chain] = nullptr;
             return 0;
         }
-        ctx->stage_cap[chain] = cnt;
     }
     return 1;
 }
@@ -866,7 +769,7 @@ int dnagpu_matrix_copy(dnagpu_ctx* ctx, int chain, dnagpu_matrix* dst, const dna
     HIPCHK(hipMemcpyAsync(dst->jest, src->jest, (size_t)src->np * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream[chain]));
     dst->form = src->form;
     if (src->form == 1) {
-        if (!dst->jrhs && dnagpu::poison_malloc(&dst->jrhs, (size_t)dst->np_max * sizeof(double)) != hipSuccess)
+        if (!dst->jrhs && dst->jrhs.alloc(dst->np_max) != hipSuccess)
             return fail(ctx, DNAGPU_ENOMEM, "matrix_copy: right-hand side of the information form");
         HIPCHK(hipMemcpyAsync(dst->jrhs, src->jrhs, (size_t)src->np * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream[chain]));
     }
@@ -953,9 +856,8 @@ int dnagpu_junction_import(dnagpu_ctx* ctx, int chain, dnagpu_matrix* m, const d
     HIPCHK(hipMemcpyAsync(&form, src + np * np + 2 * np, sizeof(double), hipMemcpyDefault, st));
     HIPCHK(hipStreamSynchronize(st));
     if (form != 0.0 && form != 1.0) return fail(ctx, DNAGPU_EINVAL, "junction_import: not a junction payload");
-    if (form == 1.0 && !m->jrhs && dnagpu::poison_malloc(&m->jrhs, (size_t)m->np_max * sizeof(double)) != hipSuccess) {
+    if (form == 1.0 && !m->jrhs && m->jrhs.alloc(m->np_max) != hipSuccess) {
         (void)hipGetLastError();
-        m->jrhs = nullptr;
         return fail(ctx, DNAGPU_ENOMEM, "junction_import: right-hand side of the information form");
     }
     HIPCHK(hipMemcpyAsync(m->F, src, np * np * sizeof(double), hipMemcpyDefault, st));
@@ -971,9 +873,8 @@ int dnagpu_junction_device_pointers(dnagpu_ctx* ctx, dnagpu_matrix* m, int as_fo
     CHK_CTX();
     if (!m || as_form > 1) return fail(ctx, DNAGPU_EINVAL, "junction_device_pointers: bad arguments");
     const int f = as_form >= 0 ? as_form : m->form;
-    if (f == 1 && !m->jrhs && dnagpu::poison_malloc(&m->jrhs, (size_t)m->np_max * sizeof(double)) != hipSuccess) {
+    if (f == 1 && !m->jrhs && m->jrhs.alloc(m->np_max) != hipSuccess) {
         (void)hipGetLastError();
-        m->jrhs = nullptr;
         return fail(ctx, DNAGPU_ENOMEM, "junction_device_pointers: right-hand side of the information form");
     }
     if (as_form >= 0) m->form = as_form;       // (about to receive a junction of that form)
@@ -1106,13 +1007,13 @@ int dnagpu_block_create(dnagpu_ctx* ctx, uint32_t blk, uint32_t n_stations, uint
     A((void**)&b.vec_k, nb * sizeof(uint32_t));
     size_t total = 0;
     for (const Slot& sl : slots) total += (sl.bytes + 255) & ~(size_t)255;
-    hipError_t e = dnagpu::poison_malloc(&b.arena, total);
+    hipError_t e = b.arena.alloc(total);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(ctx, e == hipErrorOutOfMemory ? DNAGPU_ENOMEM : DNAGPU_EHIP, "block allocation", e);
     }
     {
-        uint8_t* at = (uint8_t*)b.arena;
+        uint8_t* at = b.arena;
         for (const Slot& sl : slots) {
             *sl.p = at;
             at += (sl.bytes + 255) & ~(size_t)255;
@@ -1126,13 +1027,12 @@ int dnagpu_block_create(dnagpu_ctx* ctx, uint32_t blk, uint32_t n_stations, uint
         hipError_t em = hipMemsetAsync(b.rhs[c], 0, span, ctx->stream[c]);
         if (em != hipSuccess) {
             (void)hipGetLastError();
-            hipDeviceSynchronize();
-            hipFree(b.arena);
+            hipDeviceSynchronize();      // (then b's arena is freed)
             return fail(ctx, DNAGPU_EHIP, "block allocation: zeroing", em);
         }
     }
     ctx->osc_key = 0;       // (the visit lists of dnagpu_osc_blocks describe the blocks that existed when they were built)
-    ctx->blocks[blk] = b;
+    ctx->blocks[blk] = std::move(b);
     return DNAGPU_OK;
 }
 
@@ -1141,7 +1041,6 @@ int dnagpu_block_destroy(dnagpu_ctx* ctx, uint32_t blk) {
     Block* b = find_block(ctx, blk);
     if (!b) return fail(ctx, DNAGPU_EINVAL, "block_destroy: unknown block");
     HIPCHK(hipDeviceSynchronize());
-    free_block(*b);
     ctx->blocks.erase(blk);
     ctx->osc_key = 0;       // (dnagpu_osc_blocks: a block of the same id created later may have other stations)
     return DNAGPU_OK;
@@ -1180,7 +1079,6 @@ void dnagpu_block_table_destroy(dnagpu_ctx* ctx, dnagpu_block_table* t) {
         hipSetDevice(ctx->device);
         hipDeviceSynchronize();
     }
-    if (t->rows) hipFree(t->rows);
     delete t;
 }
 
@@ -1215,7 +1113,7 @@ int dnagpu_block_table_create(dnagpu_ctx* ctx, uint32_t n, const uint32_t* blks,
     }
     dnagpu_block_table* t = new (std::nothrow) dnagpu_block_table();
     if (!t) return fail(ctx, DNAGPU_ENOMEM, "host allocation");
-    if (dnagpu::poison_malloc(&t->rows, (size_t)n * sizeof(BlockTableRow)) != hipSuccess ||
+    if (t->rows.alloc(n) != hipSuccess ||
         hipMemcpy(t->rows, host.data(), (size_t)n * sizeof(BlockTableRow), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
         dnagpu_block_table_destroy(ctx, t);
@@ -1232,7 +1130,7 @@ int dnagpu_block_table_apply(dnagpu_ctx* ctx, int chain, const dnagpu_block_tabl
     CHK_CHAIN();
     if (!t || (mode != 0 && mode != 1) || chains < 1 || chains > DNAGPU_NUM_CHAINS) return fail(ctx, DNAGPU_EINVAL, "block_table_apply: bad arguments");
     gemm_profile_close(ctx->ws[chain]);
-    launch_block_table((const BlockTableRow*)t->rows, t->n, t->max_len, mode, mode == 0 ? DNAGPU_NUM_CHAINS : chains, ctx->stream[chain]);
+    launch_block_table(t->rows, t->n, t->max_len, mode, mode == 0 ? DNAGPU_NUM_CHAINS : chains, ctx->stream[chain]);
     HIPCHK(hipGetLastError());
     return DNAGPU_OK;
 }
@@ -1268,9 +1166,9 @@ int dnagpu_block_set_station_geo(dnagpu_ctx* ctx, uint32_t blk, const double* ll
     if (!b || (b->n_stn && (!llh || !geoid || !defl))) return fail(ctx, DNAGPU_EINVAL, "block_set_station_geo: bad arguments");
     const size_t ns = std::max<size_t>(b->n_stn, 1);
     if (!b->s_llh) {
-        HIPCHK(dnagpu::poison_malloc(&b->s_llh, 3 * ns * sizeof(double)));
-        HIPCHK(dnagpu::poison_malloc(&b->s_geoid, ns * sizeof(double)));
-        HIPCHK(dnagpu::poison_malloc(&b->s_defl, 2 * ns * sizeof(double)));
+        HIPCHK(b->s_llh.alloc(3 * ns));
+        HIPCHK(b->s_geoid.alloc(ns));
+        HIPCHK(b->s_defl.alloc(2 * ns));
     }
     if (!b->n_stn) return DNAGPU_OK;
     HIPCHK(hipMemcpy(b->s_llh, llh, 3 * (size_t)b->n_stn * sizeof(double), hipMemcpyHostToDevice));
@@ -1303,25 +1201,20 @@ int dnagpu_block_set_terrestrial(dnagpu_ctx* ctx, uint32_t blk, uint32_t n_t, co
         if (type[t] != 'D') nb += (uint32_t)(ns * (ns + 1) / 2);     // (a direction set's blocks: dnagpu_block_set_direction_sets)
         nv += (uint32_t)ns;
     }
-    for (void* p : {(void*)b->t_type, (void*)b->t_stn, (void*)b->t_blk0, (void*)b->t_vec0, (void*)b->t_val, (void*)b->t_pre, (void*)b->t_var,
-                    (void*)b->t_ih, (void*)b->t_th})
-        if (p) hipFree(p);
-    for (int c = 0; c < DNAGPU_NUM_CHAINS; ++c)
-        for (void* p : {(void*)b->tb[c], (void*)b->trow[c]})
-            if (p) hipFree(p);
-    b->t_type = nullptr;
-    b->t_stn = b->t_blk0 = b->t_vec0 = nullptr;
-    b->t_val = b->t_pre = b->t_var = b->t_ih = b->t_th = nullptr;
-    for (int c = 0; c < DNAGPU_NUM_CHAINS; ++c) b->tb[c] = b->trow[c] = nullptr;
+    b->t_type.reset();
+    for (DevBuf<uint32_t>* p : {&b->t_stn, &b->t_blk0, &b->t_vec0}) p->reset();
+    for (DevBuf<double>* p : {&b->t_val, &b->t_pre, &b->t_var, &b->t_ih, &b->t_th}) p->reset();
+    for (int c = 0; c < DNAGPU_NUM_CHAINS; ++c) {
+        b->tb[c].reset();
+        b->trow[c].reset();
+    }
     b->n_t = n_t;
     b->n_tblk = nb;
     b->n_tvec = nv;
     b->n_dsblk = 0;
     b->h_ds_ents.clear();
-    for (void* p : {(void*)b->ds_a, (void*)b->ds_b, (void*)b->ds_pq, (void*)b->ds_w, (void*)b->ds_row0, (void*)b->ds_k, (void*)b->ds_woff, (void*)b->ds_wts})
-        if (p) hipFree(p);
-    b->ds_a = b->ds_b = b->ds_pq = b->ds_w = b->ds_row0 = b->ds_k = b->ds_woff = nullptr;
-    b->ds_wts = nullptr;
+    for (DevBuf<uint32_t>* p : {&b->ds_a, &b->ds_b, &b->ds_pq, &b->ds_w, &b->ds_row0, &b->ds_k, &b->ds_woff}) p->reset();
+    b->ds_wts.reset();
     b->h_ttype.assign(type, type + n_t);
     b->h_tstn.assign(stn3, stn3 + 3 * (size_t)n_t);
     b->h_tpos.assign(cml_pos, cml_pos + n_t);
@@ -1329,29 +1222,28 @@ int dnagpu_block_set_terrestrial(dnagpu_ctx* ctx, uint32_t blk, uint32_t n_t, co
     if (cluster_cml_pos) b->h_cpos.assign(cluster_cml_pos, cluster_cml_pos + n_clusters);
     // the W b vectors of the GNSS measurements are followed by the terrestrial ones
     for (int c = 0; c < DNAGPU_NUM_CHAINS; ++c) {
-        if (b->wb[c] && b->wb_own) hipFree(b->wb[c]);      // (the arena's vectors are not freed one by one)
         b->wb[c] = nullptr;
-        HIPCHK(dnagpu::poison_malloc(&b->wb[c], std::max<size_t>((size_t)b->n_bl + nv, 1) * 3 * sizeof(double)));
+        HIPCHK(b->wb_store[c].alloc(std::max<size_t>((size_t)b->n_bl + nv, 1) * 3));
+        b->wb[c] = b->wb_store[c];
     }
-    b->wb_own = true;
     if (!n_t) return DNAGPU_OK;
-    auto upv = [&](void** dev, const void* src, size_t bytes) -> hipError_t {
-        hipError_t e = dnagpu::poison_malloc(dev, bytes);
-        if (e == hipSuccess) e = hipMemcpy(*dev, src, bytes, hipMemcpyHostToDevice);
+    auto upv = [&](auto& dev, const auto* src, size_t count) -> hipError_t {
+        hipError_t e = dev.alloc(count);
+        if (e == hipSuccess) e = hipMemcpy(dev, src, count * sizeof(*src), hipMemcpyHostToDevice);
         return e;
     };
-    HIPCHK(upv((void**)&b->t_type, type, n_t));
-    HIPCHK(upv((void**)&b->t_stn, stn3, 3 * (size_t)n_t * sizeof(uint32_t)));
-    HIPCHK(upv((void**)&b->t_blk0, blk0.data(), n_t * sizeof(uint32_t)));
-    HIPCHK(upv((void**)&b->t_vec0, vec0.data(), n_t * sizeof(uint32_t)));
-    HIPCHK(upv((void**)&b->t_val, value, n_t * sizeof(double)));
-    HIPCHK(upv((void**)&b->t_pre, pre_adj_meas, n_t * sizeof(double)));
-    HIPCHK(upv((void**)&b->t_var, variance, n_t * sizeof(double)));
-    HIPCHK(upv((void**)&b->t_ih, inst_height, n_t * sizeof(double)));
-    HIPCHK(upv((void**)&b->t_th, targ_height, n_t * sizeof(double)));
+    HIPCHK(upv(b->t_type, (const uint8_t*)type, n_t));
+    HIPCHK(upv(b->t_stn, stn3, 3 * (size_t)n_t));
+    HIPCHK(upv(b->t_blk0, blk0.data(), n_t));
+    HIPCHK(upv(b->t_vec0, vec0.data(), n_t));
+    HIPCHK(upv(b->t_val, value, n_t));
+    HIPCHK(upv(b->t_pre, pre_adj_meas, n_t));
+    HIPCHK(upv(b->t_var, variance, n_t));
+    HIPCHK(upv(b->t_ih, inst_height, n_t));
+    HIPCHK(upv(b->t_th, targ_height, n_t));
     for (int c = 0; c < DNAGPU_NUM_CHAINS; ++c) {
-        HIPCHK(dnagpu::poison_malloc(&b->tb[c], n_t * sizeof(double)));
-        HIPCHK(dnagpu::poison_malloc(&b->trow[c], 9 * (size_t)n_t * sizeof(double)));
+        HIPCHK(b->tb[c].alloc(n_t));
+        HIPCHK(b->trow[c].alloc(9 * (size_t)n_t));
     }
     return DNAGPU_OK;
 }
@@ -1394,23 +1286,16 @@ int dnagpu_block_set_direction_sets(dnagpu_ctx* ctx, uint32_t blk, uint32_t n_se
     }
     for (uint32_t t = 0; t < n_t; ++t)
         if (b->h_ttype[t] == 'D' && !in_set[t]) return fail(ctx, DNAGPU_EINVAL, "block_set_direction_sets: a type D entry belongs to no set");
-    auto up32 = [&](uint32_t** dev, const std::vector<uint32_t>& v) -> hipError_t {
-        hipError_t e = dnagpu::poison_malloc((void**)dev, std::max<size_t>(v.size(), 1) * sizeof(uint32_t));
-        if (e == hipSuccess && !v.empty()) e = hipMemcpy(*dev, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        return e;
-    };
-    for (void* p : {(void*)b->ds_a, (void*)b->ds_b, (void*)b->ds_pq, (void*)b->ds_w, (void*)b->ds_row0, (void*)b->ds_k, (void*)b->ds_woff, (void*)b->ds_wts})
-        if (p) hipFree(p);
-    b->ds_a = b->ds_b = b->ds_pq = b->ds_w = b->ds_row0 = b->ds_k = b->ds_woff = nullptr;
-    b->ds_wts = nullptr;
-    HIPCHK(up32(&b->ds_a, ea));
-    HIPCHK(up32(&b->ds_b, eb));
-    HIPCHK(up32(&b->ds_pq, epq));
-    HIPCHK(up32(&b->ds_w, ew));
-    HIPCHK(up32(&b->ds_row0, row0));
-    HIPCHK(up32(&b->ds_k, kk));
-    HIPCHK(up32(&b->ds_woff, woff));
-    HIPCHK(dnagpu::poison_malloc(&b->ds_wts, std::max<size_t>(wtot, 1) * sizeof(double)));
+    for (DevBuf<uint32_t>* p : {&b->ds_a, &b->ds_b, &b->ds_pq, &b->ds_w, &b->ds_row0, &b->ds_k, &b->ds_woff}) p->reset();
+    b->ds_wts.reset();
+    HIPCHK(upload_list(b->ds_a, ea));
+    HIPCHK(upload_list(b->ds_b, eb));
+    HIPCHK(upload_list(b->ds_pq, epq));
+    HIPCHK(upload_list(b->ds_w, ew));
+    HIPCHK(upload_list(b->ds_row0, row0));
+    HIPCHK(upload_list(b->ds_k, kk));
+    HIPCHK(upload_list(b->ds_woff, woff));
+    HIPCHK(b->ds_wts.alloc(std::max<size_t>(wtot, 1)));
     if (wtot) HIPCHK(hipMemcpy(b->ds_wts, weights, wtot * sizeof(double), hipMemcpyHostToDevice));
     b->n_dsblk = (uint32_t)ea.size();
     return DNAGPU_OK;
@@ -1532,26 +1417,17 @@ int dnagpu_block_set_clusters(dnagpu_ctx* ctx, uint32_t blk, const uint32_t* stn
     }
     for (uint32_t s = 0; s < ns; ++s) ioff[s + 1] += ioff[s];
 
-    for (void* p : {(void*)b->pair_row, (void*)b->pair_col, (void*)b->pair_off, (void*)b->pair_ent, (void*)b->inc_off, (void*)b->inc,
-                    (void*)b->Wblk})
-        if (p) hipFree(p);
-    b->pair_row = b->pair_col = b->pair_off = b->pair_ent = b->inc_off = b->inc = nullptr;
-    b->Wblk = nullptr;
+    for (DevBuf<uint32_t>* p : {&b->pair_row, &b->pair_col, &b->pair_off, &b->pair_ent, &b->inc_off, &b->inc}) p->reset();
+    b->Wblk.reset();
     b->n_pairs = (uint32_t)prow.size();
     b->n_wblk = n_wblk;
-    auto up = [&](uint32_t** dev, const std::vector<uint32_t>& v) -> hipError_t {
-        size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(uint32_t);
-        hipError_t e = dnagpu::poison_malloc((void**)dev, bytes);
-        if (e == hipSuccess && !v.empty()) e = hipMemcpy(*dev, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        return e;
-    };
-    HIPCHK(up(&b->pair_row, prow));
-    HIPCHK(up(&b->pair_col, pcol));
-    HIPCHK(up(&b->pair_off, poff));
-    HIPCHK(up(&b->pair_ent, pent));
-    HIPCHK(up(&b->inc_off, ioff));
-    HIPCHK(up(&b->inc, inc));
-    HIPCHK(dnagpu::poison_malloc(&b->Wblk, std::max<size_t>((size_t)n_wblk + (size_t)DNAGPU_NUM_CHAINS * ((size_t)b->n_tblk + b->n_dsblk), 1) * 9 * sizeof(double)));
+    HIPCHK(upload_list(b->pair_row, prow));
+    HIPCHK(upload_list(b->pair_col, pcol));
+    HIPCHK(upload_list(b->pair_off, poff));
+    HIPCHK(upload_list(b->pair_ent, pent));
+    HIPCHK(upload_list(b->inc_off, ioff));
+    HIPCHK(upload_list(b->inc, inc));
+    HIPCHK(b->Wblk.alloc(std::max<size_t>((size_t)n_wblk + (size_t)DNAGPU_NUM_CHAINS * ((size_t)b->n_tblk + b->n_dsblk), 1) * 9));
     if (!m) return DNAGPU_OK;
     HIPCHK(hipMemcpy(b->s1, stn1, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(b->s2, stn2, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -1573,10 +1449,10 @@ int dnagpu_block_set_clusters(dnagpu_ctx* ctx, uint32_t blk, const uint32_t* stn
         }
     int bad = 0x7fffffff;
     if (!dst.empty()) {
-        double* vtmp = nullptr;
-        uint32_t* dtmp = nullptr;
-        HIPCHK(dnagpu::poison_malloc(&vtmp, v6.size() * sizeof(double)));
-        hipError_t e = dnagpu::poison_malloc(&dtmp, dst.size() * sizeof(uint32_t));
+        DevBuf<double> vtmp;
+        DevBuf<uint32_t> dtmp;
+        HIPCHK(vtmp.alloc(v6.size()));
+        hipError_t e = dtmp.alloc(dst.size());
         if (e == hipSuccess) e = hipMemcpy(vtmp, v6.data(), v6.size() * sizeof(double), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(dtmp, dst.data(), dst.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(ctx->bad_dev, &bad, sizeof(int), hipMemcpyHostToDevice);
@@ -1585,8 +1461,6 @@ int dnagpu_block_set_clusters(dnagpu_ctx* ctx, uint32_t blk, const uint32_t* stn
             e = hipStreamSynchronize(ctx->stream[0]);
         }
         if (e == hipSuccess) e = hipMemcpy(&bad, ctx->bad_dev, sizeof(int), hipMemcpyDeviceToHost);
-        hipFree(vtmp);
-        if (dtmp) hipFree(dtmp);
         if (e != hipSuccess) return fail(ctx, DNAGPU_EHIP, "block_set_clusters: weights", e);
         if (bad != 0x7fffffff) {
             char buf[160];
@@ -1810,16 +1684,15 @@ int dnagpu_osc_reset(dnagpu_ctx* ctx, size_t n_stations) {
     CHK_CTX();
     if (ctx->osc_stations != n_stations) {
         HIPCHK(hipDeviceSynchronize());
-        for (void* p : {(void*)ctx->osc_prev, (void*)ctx->osc_seen, (void*)ctx->osc_cnt})
-            if (p) hipFree(p);
-        ctx->osc_prev = nullptr;
-        ctx->osc_seen = ctx->osc_cnt = nullptr;
+        ctx->osc_prev.reset();
+        ctx->osc_seen.reset();
+        ctx->osc_cnt.reset();
         ctx->osc_stations = 0;
         ctx->osc_key = 0;       // (the visit lists of dnagpu_osc_blocks are per station of the network)
         if (n_stations) {
-            hipError_t e = dnagpu::poison_malloc(&ctx->osc_prev, 3 * n_stations * sizeof(double));
-            if (e == hipSuccess) e = dnagpu::poison_malloc(&ctx->osc_seen, n_stations * sizeof(uint32_t));
-            if (e == hipSuccess) e = dnagpu::poison_malloc(&ctx->osc_cnt, n_stations * sizeof(uint32_t));
+            hipError_t e = ctx->osc_prev.alloc(3 * n_stations);
+            if (e == hipSuccess) e = ctx->osc_seen.alloc(n_stations);
+            if (e == hipSuccess) e = ctx->osc_cnt.alloc(n_stations);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
                 return fail(ctx, DNAGPU_ENOMEM, "oscillation diagnostics", e);
@@ -1827,7 +1700,7 @@ int dnagpu_osc_reset(dnagpu_ctx* ctx, size_t n_stations) {
             ctx->osc_stations = n_stations;
         }
     }
-    if (!ctx->osc_flagged) HIPCHK(dnagpu::poison_malloc(&ctx->osc_flagged, sizeof(uint32_t)));
+    if (!ctx->osc_flagged) HIPCHK(ctx->osc_flagged.alloc(1));
     hipStream_t st = ctx->stream[0];
     if (n_stations) {
         HIPCHK(hipMemsetAsync(ctx->osc_seen, 0, n_stations * sizeof(uint32_t), st));
@@ -1843,7 +1716,7 @@ int dnagpu_block_keep_corrections(dnagpu_ctx* ctx, int chain, uint32_t blk) {
     Block* b = find_block(ctx, blk);
     if (!b || !b->corr[chain]) return fail(ctx, DNAGPU_EINVAL, "block_keep_corrections: bad arguments");
     if (!b->n_stn) return DNAGPU_OK;
-    if (!b->corr_keep) HIPCHK(dnagpu::poison_malloc(&b->corr_keep, (size_t)b->n_stn * 3 * sizeof(double)));
+    if (!b->corr_keep) HIPCHK(b->corr_keep.alloc((size_t)b->n_stn * 3));
     HIPCHK(hipMemcpyAsync(b->corr_keep, b->corr[chain], (size_t)b->n_stn * 3 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream[chain]));
     return DNAGPU_OK;
 }
@@ -1857,8 +1730,8 @@ int dnagpu_osc_block(dnagpu_ctx* ctx, uint32_t blk, int corr_chain, const uint32
     if (!b->osc_gidx && b->n_stn) {
         for (uint32_t s = 0; s < b->n_stn; ++s)
             if (stations[s] >= ctx->osc_stations) return fail(ctx, DNAGPU_EINVAL, "osc_block: station out of range");
-        HIPCHK(dnagpu::poison_malloc(&b->osc_gidx, (size_t)b->n_stn * sizeof(uint32_t)));
-        HIPCHK(dnagpu::poison_malloc(&b->osc_visit, (size_t)b->n_stn * sizeof(uint32_t)));
+        HIPCHK(b->osc_gidx.alloc(b->n_stn));
+        HIPCHK(b->osc_visit.alloc(b->n_stn));
         HIPCHK(hipMemcpy(b->osc_gidx, stations, (size_t)b->n_stn * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     launch_osc_update(corr, b->osc_gidx, b->n_stn, ctx->osc_prev, ctx->osc_seen, ctx->osc_cnt, b->osc_visit, ctx->osc_flagged, st);
@@ -1877,8 +1750,8 @@ int dnagpu_osc_blocks(dnagpu_ctx* ctx, uint32_t n, const uint32_t* blks, const i
         if (!b->osc_gidx && b->n_stn) {
             for (uint32_t s = 0; s < b->n_stn; ++s)
                 if (stations[q][s] >= ctx->osc_stations) return fail(ctx, DNAGPU_EINVAL, "osc_blocks: station out of range");
-            HIPCHK(dnagpu::poison_malloc(&b->osc_gidx, (size_t)b->n_stn * sizeof(uint32_t)));
-            HIPCHK(dnagpu::poison_malloc(&b->osc_visit, (size_t)b->n_stn * sizeof(uint32_t)));
+            HIPCHK(b->osc_gidx.alloc(b->n_stn));
+            HIPCHK(b->osc_visit.alloc(b->n_stn));
             HIPCHK(hipMemcpy(b->osc_gidx, stations[q], (size_t)b->n_stn * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
         rows[q] = {corr, b->osc_gidx, b->osc_visit, b->n_stn};
@@ -1899,10 +1772,9 @@ int dnagpu_osc_blocks(dnagpu_ctx* ctx, uint32_t n, const uint32_t* blks, const i
         }
     } else {
         HIPCHK(hipStreamSynchronize(st));
-        for (void* p : {ctx->osc_rows, (void*)ctx->osc_off, ctx->osc_visits})
-            if (p) hipFree(p);
-        ctx->osc_rows = ctx->osc_visits = nullptr;
-        ctx->osc_off = nullptr;
+        ctx->osc_rows.reset();
+        ctx->osc_off.reset();
+        ctx->osc_visits.reset();
         ctx->osc_key = 0;
         std::vector<uint32_t> off(ctx->osc_stations + 1, 0);
         for (uint32_t q = 0; q < n; ++q)
@@ -1912,9 +1784,9 @@ int dnagpu_osc_blocks(dnagpu_ctx* ctx, uint32_t n, const uint32_t* blks, const i
         std::vector<uint2> visits(off.back() ? off.back() : 1);
         for (uint32_t q = 0; q < n; ++q)          // (blocks in the order given: a station's visits end up in block order)
             for (uint32_t s = 0; s < rows[q].n_stn; ++s) visits[fill[stations[q][s]]++] = make_uint2(q, s);
-        HIPCHK(dnagpu::poison_malloc(&ctx->osc_rows, (size_t)n * sizeof(OscRow)));
-        HIPCHK(dnagpu::poison_malloc(&ctx->osc_off, off.size() * sizeof(uint32_t)));
-        HIPCHK(dnagpu::poison_malloc(&ctx->osc_visits, visits.size() * sizeof(uint2)));
+        HIPCHK(ctx->osc_rows.alloc(n));
+        HIPCHK(ctx->osc_off.alloc(off.size()));
+        HIPCHK(ctx->osc_visits.alloc(visits.size()));
         HIPCHK(hipMemcpy(ctx->osc_rows, rows.data(), (size_t)n * sizeof(OscRow), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(ctx->osc_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(ctx->osc_visits, visits.data(), visits.size() * sizeof(uint2), hipMemcpyHostToDevice));
@@ -1922,7 +1794,7 @@ int dnagpu_osc_blocks(dnagpu_ctx* ctx, uint32_t n, const uint32_t* blks, const i
         ctx->osc_blks.assign(blks, blks + n);
         ctx->osc_key = key;
     }
-    launch_osc_update_stations((const OscRow*)ctx->osc_rows, ctx->osc_off, ctx->osc_visits, (uint32_t)ctx->osc_stations, ctx->osc_prev, ctx->osc_seen,
+    launch_osc_update_stations(ctx->osc_rows, ctx->osc_off, ctx->osc_visits, (uint32_t)ctx->osc_stations, ctx->osc_prev, ctx->osc_seen,
                                ctx->osc_cnt, ctx->osc_flagged, st);
     HIPCHK(hipGetLastError());
     return DNAGPU_OK;
@@ -1977,8 +1849,8 @@ int dnagpu_add_diag3x3(dnagpu_ctx* ctx, int chain, dnagpu_matrix* m, const uint3
         if (3 * (uint64_t)stn[i] + 2 >= m->n) return fail(ctx, DNAGPU_EINVAL, "add_diag3x3: station out of range");
     uint32_t* dstn = nullptr;
     double* dw = nullptr;
-    int rc = stage_u32(ctx, chain, stn, k, &dstn);
-    if (!rc) rc = stage_f64(ctx, chain, w9, k * 9, &dw);
+    int rc = stage(ctx, chain, stn, k, &dstn);
+    if (!rc) rc = stage(ctx, chain, w9, k * 9, &dw);
     if (rc) return rc;
     launch_add_diag3x3(m->F, m->np, dstn, dw, (uint32_t)k, sign < 0 ? -1.0 : 1.0, ctx->stream[chain]);
     return DNAGPU_OK;
@@ -2057,7 +1929,7 @@ int dnagpu_junction_gather(dnagpu_ctx* ctx, int chain, uint32_t blk_from, const 
     }
     if (!k) return DNAGPU_OK;
     uint32_t* didx = nullptr;
-    int rc = stage_u32(ctx, chain, idx_from, k, &didx);
+    int rc = stage(ctx, chain, idx_from, k, &didx);
     if (rc) return rc;
     if (src) launch_junction_gather(src->F, src->np, didx, (uint32_t)k, jm->F, jm->np, ctx->stream[chain]);
     launch_gather_vec3(b->x_est[chain], didx, (uint32_t)k, jm->jest, ctx->stream[chain]);
@@ -2115,18 +1987,14 @@ int schur_order(dnagpu_ctx* ctx, Block* b, const uint32_t* idx_out, size_t k, ui
         // a launch that still uses one of them was enqueued long before (the lists retired LAST stay)
         if (b->retired.size() >= 12) {
             HIPCHK(hipDeviceSynchronize());
-            for (size_t i = 0; i + 6 < b->retired.size(); ++i) hipFree(b->retired[i]);
-            b->retired.erase(b->retired.begin(), b->retired.end() - 6);
+            b->retired.erase(b->retired.begin(), b->retired.end() - 6);        // (frees all but the last 6)
         }
-        if (b->schur_map[slot]) b->retired.push_back(b->schur_map[slot]);
-        if (b->schur_idx[slot]) b->retired.push_back(b->schur_idx[slot]);
-        if (b->schur_spos[slot]) b->retired.push_back(b->schur_spos[slot]);
-        b->schur_map[slot] = nullptr;
-        b->schur_idx[slot] = nullptr;
-        b->schur_spos[slot] = nullptr;
-        HIPCHK(dnagpu::poison_malloc(&b->schur_map[slot], (size_t)npp * sizeof(int32_t)));
-        HIPCHK(dnagpu::poison_malloc(&b->schur_idx[slot], k * sizeof(uint32_t)));
-        HIPCHK(dnagpu::poison_malloc(&b->schur_spos[slot], (size_t)b->n_stn * sizeof(uint32_t)));
+        if (b->schur_map[slot]) b->retired.emplace_back(b->schur_map[slot].release());
+        if (b->schur_idx[slot]) b->retired.emplace_back(b->schur_idx[slot].release());
+        if (b->schur_spos[slot]) b->retired.emplace_back(b->schur_spos[slot].release());
+        HIPCHK(b->schur_map[slot].alloc(npp));
+        HIPCHK(b->schur_idx[slot].alloc(k));
+        HIPCHK(b->schur_spos[slot].alloc(b->n_stn));
         HIPCHK(hipMemcpy(b->schur_spos[slot], spos.data(), (size_t)b->n_stn * sizeof(uint32_t), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(b->schur_map[slot], map.data(), (size_t)npp * sizeof(int32_t), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(b->schur_idx[slot], idx_out, k * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -2181,8 +2049,8 @@ int schur_eliminate(dnagpu_ctx* ctx, int chain, Block* b, dnagpu_matrix* m, cons
             if (form->n_con) {
                 for (size_t i = 0; i < form->n_con; ++i)
                     if (form->con_stn[i] >= b->n_stn) return fail(ctx, DNAGPU_EINVAL, "schur: constraint station out of range");
-                int rs = stage_u32(ctx, chain, form->con_stn, form->n_con, &dstn);
-                if (!rs) rs = stage_f64(ctx, chain, form->con_w9, form->n_con * 9, &dw);
+                int rs = stage(ctx, chain, form->con_stn, form->n_con, &dstn);
+                if (!rs) rs = stage(ctx, chain, form->con_w9, form->n_con * 9, &dw);
                 if (rs) return rs;
             }
             HbmTimed timed(ctx, chain, DNAGPU_HBM_FORM_ORDERED, 4.0 * (double)npp * npp);
@@ -2256,9 +2124,8 @@ int dnagpu_schur_carry(dnagpu_ctx* ctx, int chain, uint32_t blk, dnagpu_matrix* 
         // with the estimates they were formed at; the next block adds S to its normals and r + S (those estimates - its own) to its
         // right-hand side (dnagpu_junction_rhs) -- what the estimates x + S^-1 r weighted by S contribute, without S^-1: no inverse of
         // the complement (nj^3 flops and, for a 450-unknown junction, half of the step's launches)
-        if (!jm->jrhs && dnagpu::poison_malloc(&jm->jrhs, (size_t)jm->np_max * sizeof(double)) != hipSuccess) {
+        if (!jm->jrhs && jm->jrhs.alloc(jm->np_max) != hipSuccess) {
             (void)hipGetLastError();
-            jm->jrhs = nullptr;
             return fail(ctx, DNAGPU_ENOMEM, "schur_carry: right-hand side of the information form");
         }
         launch_schur_extract(T, ldt, nj, npj, jm->F, nullptr, jm->jrhs, st);
@@ -2297,9 +2164,8 @@ int dnagpu_schur_carry_keep(dnagpu_ctx* ctx, int chain, uint32_t blk, dnagpu_mat
     hipStream_t st = ctx->stream[chain];
     jm->n = nj;
     jm->np = npj;
-    if (!jm->jrhs && dnagpu::poison_malloc(&jm->jrhs, (size_t)jm->np_max * sizeof(double)) != hipSuccess) {
+    if (!jm->jrhs && jm->jrhs.alloc(jm->np_max) != hipSuccess) {
         (void)hipGetLastError();
-        jm->jrhs = nullptr;
         return fail(ctx, DNAGPU_ENOMEM, "schur_carry: right-hand side of the information form");
     }
     launch_schur_extract(T, ldt, nj, npj, jm->F, nullptr, jm->jrhs, st);
@@ -2326,7 +2192,7 @@ int dnagpu_schur_carry_rhs(dnagpu_ctx* ctx, int chain, uint32_t blk, const uint3
     if (!rc) rc = ensure_symv(ctx, chain, keep->npp);
     if (rc) return rc;
     uint32_t* didx = nullptr;
-    rc = stage_u32(ctx, chain, idx_out, k, &didx);
+    rc = stage(ctx, chain, idx_out, k, &didx);
     if (rc) return rc;
     InvWorkspace& ws = ctx->ws[chain];
     hipStream_t st = ctx->stream[chain];
@@ -2367,9 +2233,9 @@ int dnagpu_chain_step_rhs(dnagpu_ctx* ctx, int chain, uint32_t rblk, uint32_t sr
         if (idx_in[i] >= rb->n_stn) return fail(ctx, DNAGPU_EINVAL, "chain_step_rhs: station out of range");
     ChainRhsStep a{};
     uint32_t *dkeep = nullptr, *din = nullptr, *dout = nullptr;
-    int rc = stage_u32(ctx, chain, idx_keep, k_keep, &dkeep);
-    if (!rc) rc = stage_u32(ctx, chain, idx_out, k_out, &dout);
-    if (!rc && jm_in) rc = stage_u32(ctx, chain, idx_in, k_in, &din);
+    int rc = stage(ctx, chain, idx_keep, k_keep, &dkeep);
+    if (!rc) rc = stage(ctx, chain, idx_out, k_out, &dout);
+    if (!rc && jm_in) rc = stage(ctx, chain, idx_in, k_in, &din);
     if (rc) return rc;
     // (three lists through ONE staging buffer would overwrite each other: all of them must have come from the cache)
     if (dkeep == ctx->scr_u32[chain] || dout == ctx->scr_u32[chain] || (jm_in && din == ctx->scr_u32[chain])) return DNAGPU_ETOOLARGE;
@@ -2397,10 +2263,6 @@ void dnagpu_small_batch_destroy(dnagpu_ctx* ctx, dnagpu_small_batch* sb) {
         hipSetDevice(ctx->device);
         hipDeviceSynchronize();
     }
-    if (sb->table) hipFree(sb->table);
-    if (sb->result) hipFree(sb->result);
-    if (sb->result_host) hipHostFree(sb->result_host);
-    for (uint32_t* p : sb->idx_dev) hipFree(p);
     delete sb;
 }
 
@@ -2418,7 +2280,7 @@ int dnagpu_small_batch_create(dnagpu_ctx* ctx, uint32_t n, const uint32_t* blks,
         dnagpu_small_batch_destroy(ctx, sb);
         return rc;
     };
-    if (dnagpu::poison_malloc(&sb->result, (size_t)2 * n * sizeof(double)) != hipSuccess || hipHostMalloc(&sb->result_host, (size_t)2 * n * sizeof(double)) != hipSuccess) {
+    if (sb->result.alloc((size_t)2 * n) != hipSuccess || sb->result_host.alloc((size_t)2 * n) != hipSuccess) {
         (void)hipGetLastError();
         return bail(fail(ctx, DNAGPU_ENOMEM, "small_batch_create: result buffers"));
     }
@@ -2434,15 +2296,12 @@ int dnagpu_small_batch_create(dnagpu_ctx* ctx, uint32_t n, const uint32_t* blks,
             if (jm[e] && ix[e]) idx_all.insert(idx_all.end(), ix[e], ix[e] + kk[e]);
         }
     }
-    uint32_t* idx_dev_all = nullptr;
     if (!idx_all.empty()) {
-        if (dnagpu::poison_malloc(&idx_dev_all, idx_all.size() * sizeof(uint32_t)) != hipSuccess ||
-            hipMemcpy(idx_dev_all, idx_all.data(), idx_all.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+        if (sb->idx_dev.alloc(idx_all.size()) != hipSuccess ||
+            hipMemcpy(sb->idx_dev, idx_all.data(), idx_all.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
             (void)hipGetLastError();
-            if (idx_dev_all) hipFree(idx_dev_all);
             return bail(fail(ctx, DNAGPU_ENOMEM, "small_batch_create: station lists"));
         }
-        sb->idx_dev.push_back(idx_dev_all);
     }
     for (uint32_t q = 0; q < n; ++q) {
         Block* b = find_block(ctx, blks[q]);
@@ -2453,9 +2312,8 @@ int dnagpu_small_batch_create(dnagpu_ctx* ctx, uint32_t n, const uint32_t* blks,
         if (!p->spine || !p->factored || p->n != 3 * b->n_stn || red[q]->n != p->nj || p->npp > SMALL_STEP_MAX || 3 * b->n_stn > SMALL_STEP_MAX ||
             blocks.size() > (size_t)SMALL_STEP_BLOCKS || b->n_t || b->n_dsblk)
             return bail(DNAGPU_ETOOLARGE);
-        if (last[q] && !b->corr_keep && dnagpu::poison_malloc(&b->corr_keep, (size_t)b->n_stn * 3 * sizeof(double)) != hipSuccess) {
+        if (last[q] && !b->corr_keep && b->corr_keep.alloc((size_t)b->n_stn * 3) != hipSuccess) {
             (void)hipGetLastError();
-            b->corr_keep = nullptr;
             return bail(fail(ctx, DNAGPU_ENOMEM, "small_batch_create: corrections set aside"));
         }
         SmallBlockDesc& d = host[q];
@@ -2479,13 +2337,13 @@ int dnagpu_small_batch_create(dnagpu_ctx* ctx, uint32_t n, const uint32_t* blks,
             if (!ix[e] || jm[e]->n != 3 * kk[e] || jm[e]->form != 1 || !jm[e]->jrhs || 3 * kk[e] > SMALL_STEP_MAX) return bail(DNAGPU_ETOOLARGE);
             for (size_t i = 0; i < kk[e]; ++i)
                 if (ix[e][i] >= b->n_stn) return bail(fail(ctx, DNAGPU_EINVAL, "small_batch_create: station out of range"));
-            uint32_t* dev = idx_dev_all + idx_at[2 * (size_t)q + e];
+            uint32_t* dev = sb->idx_dev + idx_at[2 * (size_t)q + e];
             d.J[e] = jm[e]->F; d.jest[e] = jm[e]->jest; d.jrhs[e] = jm[e]->jrhs; d.jidx[e] = dev; d.jk[e] = (uint32_t)kk[e]; d.jnp[e] = jm[e]->np;
         }
         d.last = last[q] ? 1u : 0u;
         d.result = sb->result + 2 * (size_t)q;
     }
-    if (dnagpu::poison_malloc(&sb->table, (size_t)n * sizeof(SmallBlockDesc)) != hipSuccess ||
+    if (sb->table.alloc(n) != hipSuccess ||
         hipMemcpy(sb->table, host.data(), (size_t)n * sizeof(SmallBlockDesc), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
         return bail(fail(ctx, DNAGPU_ENOMEM, "small_batch_create: block table"));
@@ -2500,7 +2358,7 @@ int dnagpu_small_batch_condense(dnagpu_ctx* ctx, int chain, dnagpu_small_batch* 
     CHK_CHAIN();
     if (!sb || !sb->n) return fail(ctx, DNAGPU_EINVAL, "small_batch_condense: bad arguments");
     gemm_profile_close(ctx->ws[chain]);
-    launch_small_condense((const SmallBlockDesc*)sb->table, sb->n, ctx->stream[chain]);
+    launch_small_condense(sb->table, sb->n, ctx->stream[chain]);
     HIPCHK(hipGetLastError());
     return DNAGPU_OK;
 }
@@ -2511,7 +2369,7 @@ int dnagpu_small_batch_solve(dnagpu_ctx* ctx, int chain, dnagpu_small_batch* sb,
     if (!sb || !sb->n || !max_corr) return fail(ctx, DNAGPU_EINVAL, "small_batch_solve: bad arguments");
     hipStream_t st = ctx->stream[chain];
     gemm_profile_close(ctx->ws[chain]);
-    launch_small_solve((const SmallBlockDesc*)sb->table, sb->n, st);
+    launch_small_solve(sb->table, sb->n, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(sb->result_host, sb->result, (size_t)2 * sb->n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -2527,9 +2385,10 @@ int dnagpu_partial_create(dnagpu_ctx* ctx, uint32_t n_max, uint32_t k_max, dnagp
     if (!p) return fail(ctx, DNAGPU_ENOMEM, "host allocation");
     p->k_cap = pad128(k_max + 1);
     p->n_cap = pad128(n_max - k_max ? n_max - k_max : 1) + p->k_cap;
-    hipError_t e = dnagpu::poison_malloc(&p->X, (size_t)p->n_cap * p->n_cap * sizeof(double));
-    if (e == hipSuccess) e = dnagpu::poison_malloc(&p->WK, (size_t)p->k_cap * p->n_cap * sizeof(double));
-    if (e == hipSuccess) e = dnagpu::poison_malloc(&p->map, (size_t)p->n_cap * sizeof(int32_t));
+    hipError_t e = p->X_own.alloc((size_t)p->n_cap * p->n_cap);
+    p->X = p->X_own;
+    if (e == hipSuccess) e = p->WK.alloc((size_t)p->k_cap * p->n_cap);
+    if (e == hipSuccess) e = p->map.alloc(p->n_cap);
     if (e != hipSuccess) {
         dnagpu_partial_destroy(ctx, p);
         return fail(ctx, e == hipErrorOutOfMemory ? DNAGPU_ENOMEM : DNAGPU_EHIP, "retained factor allocation", e);
@@ -2552,8 +2411,8 @@ int dnagpu_partial_create_in(dnagpu_ctx* ctx, uint32_t n_max, uint32_t k_max, dn
     }
     p->store = store;
     p->X = store->F;
-    hipError_t e = dnagpu::poison_malloc(&p->WK, (size_t)p->k_cap * p->n_cap * sizeof(double));
-    if (e == hipSuccess) e = dnagpu::poison_malloc(&p->map, (size_t)p->n_cap * sizeof(int32_t));
+    hipError_t e = p->WK.alloc((size_t)p->k_cap * p->n_cap);
+    if (e == hipSuccess) e = p->map.alloc(p->n_cap);
     if (e != hipSuccess) {
         dnagpu_partial_destroy(ctx, p);
         return fail(ctx, e == hipErrorOutOfMemory ? DNAGPU_ENOMEM : DNAGPU_EHIP, "retained factor allocation", e);
@@ -2577,11 +2436,9 @@ int dnagpu_partial_create_spine(dnagpu_ctx* ctx, uint32_t n_max, uint32_t k_max,
     p->store = store;
     p->spine = true;
     hipError_t e = hipSuccess;
-    if (store)
-        p->X = store->F;
-    else
-        e = dnagpu::poison_malloc(&p->X, (size_t)p->n_cap * p->n_cap * sizeof(double));
-    if (e == hipSuccess) e = dnagpu::poison_malloc(&p->map, (size_t)p->n_cap * sizeof(int32_t));
+    if (!store) e = p->X_own.alloc((size_t)p->n_cap * p->n_cap);
+    p->X = store ? store->F.get() : p->X_own.get();
+    if (e == hipSuccess) e = p->map.alloc(p->n_cap);
     if (e != hipSuccess) {
         dnagpu_partial_destroy(ctx, p);
         return fail(ctx, e == hipErrorOutOfMemory ? DNAGPU_ENOMEM : DNAGPU_EHIP, "retained factor allocation", e);
@@ -2596,9 +2453,6 @@ void dnagpu_partial_destroy(dnagpu_ctx* ctx, dnagpu_partial* p) {
         hipSetDevice(ctx->device);
         hipDeviceSynchronize();
     }
-    if (p->X && !p->store) hipFree(p->X);
-    if (p->WK) hipFree(p->WK);
-    if (p->map) hipFree(p->map);
     delete p;
 }
 
@@ -2830,37 +2684,31 @@ int ensure_batch_ws(dnagpu_ctx* ctx, int chain, int nb, uint32_t npp, uint32_t w
     int rc = ensure_ws(ctx, chain, npp);
     if (rc) return rc;
     InvWorkspace& ws = ctx->ws[chain];
+    auto free_members = [&] {
+        for (int q = 0; q < BATCH_MAX; ++q) {
+            ws.bX[q].reset();
+            ws.bW[q].reset();
+        }
+    };
     if (nb > 1 && g_fail_batch_ws.load() > 0 && g_fail_batch_ws.fetch_sub(1) > 0) {
         HIPCHK(hipStreamSynchronize(ctx->stream[chain]));
-        for (int q = 1; q < BATCH_MAX; ++q) {
-            if (ws.bX[q]) hipFree(ws.bX[q]);
-            if (ws.bW[q]) hipFree(ws.bW[q]);
-            ws.bX[q] = ws.bW[q] = nullptr;
-        }
+        free_members();
         return fail(ctx, DNAGPU_ENOMEM, "batch workspace allocation (injected)");
     }
     if (ws.bnp_cap < npp || ws.bw_cols < wcols) {
         HIPCHK(hipStreamSynchronize(ctx->stream[chain]));
-        for (int b = 0; b < BATCH_MAX; ++b) {
-            if (ws.bX[b]) hipFree(ws.bX[b]);
-            if (ws.bW[b]) hipFree(ws.bW[b]);
-            ws.bX[b] = ws.bW[b] = nullptr;
-        }
+        free_members();
         ws.bnp_cap = std::max(ws.bnp_cap, npp);
         ws.bw_cols = std::max(ws.bw_cols, wcols);
     }
     for (int b = 1; b < nb; ++b) {
         hipError_t e = hipSuccess;
-        if (!ws.bX[b]) e = dnagpu::poison_malloc(&ws.bX[b], (size_t)ws.bnp_cap * ws.bnp_cap * sizeof(double));
-        if (e == hipSuccess && !ws.bW[b]) e = dnagpu::poison_malloc(&ws.bW[b], ((size_t)ws.bw_cols + 128) * ws.bnp_cap * sizeof(double));
+        if (!ws.bX[b]) e = ws.bX[b].alloc((size_t)ws.bnp_cap * ws.bnp_cap);
+        if (e == hipSuccess && !ws.bW[b]) e = ws.bW[b].alloc(((size_t)ws.bw_cols + 128) * ws.bnp_cap);
         if (e != hipSuccess) {
             (void)hipGetLastError();
             // nothing half allocated stays behind: the caller falls back to one member at a time and needs the memory for that
-            for (int q = 1; q < BATCH_MAX; ++q) {
-                if (ws.bX[q]) hipFree(ws.bX[q]);
-                if (ws.bW[q]) hipFree(ws.bW[q]);
-                ws.bX[q] = ws.bW[q] = nullptr;
-            }
+            free_members();
             return fail(ctx, e == hipErrorOutOfMemory ? DNAGPU_ENOMEM : DNAGPU_EHIP, "batch workspace allocation", e);
         }
     }
@@ -2911,9 +2759,6 @@ void dnagpu_chain_plan_destroy(dnagpu_ctx* ctx, dnagpu_chain_plan* plan) {
         hipSetDevice(ctx->device);
         hipDeviceSynchronize();
     }
-    if (plan->table) hipFree(plan->table);
-    if (plan->blob) hipFree(plan->blob);
-    if (plan->factors) hipFree(plan->factors);
     delete plan;
 }
 
@@ -2925,20 +2770,12 @@ int dnagpu_chain_plan_create(dnagpu_ctx* ctx, size_t n_steps, const dnagpu_chain
     if (!n_steps || !steps || !n_batches || !batch_first || batch_first[0] != 0 || batch_first[n_batches] != n_steps)
         return fail(ctx, DNAGPU_EINVAL, "chain_plan_create: bad arguments");
     // (whatever the plan has allocated on the device goes with it on every error path below: its factors alone can be 96 GB)
-    struct PlanDeleter {
-        void operator()(dnagpu_chain_plan* p) const {
-            if (!p) return;
-            for (void* q : {p->table, p->blob, (void*)p->factors})
-                if (q) hipFree(q);
-            delete p;
-        }
-    };
-    std::unique_ptr<dnagpu_chain_plan, PlanDeleter> plan(new (std::nothrow) dnagpu_chain_plan());
+    std::unique_ptr<dnagpu_chain_plan> plan(new (std::nothrow) dnagpu_chain_plan());
     if (!plan) return fail(ctx, DNAGPU_ENOMEM, "host allocation");
     // a junction's right-hand side, allocated on first use: no memory for it is DNAGPU_ENOMEM (the caller then runs the chains step by step)
     auto ensure_jrhs = [&](dnagpu_matrix* m) -> int {
         if (m->jrhs) return DNAGPU_OK;
-        hipError_t e = dnagpu::poison_malloc(&m->jrhs, (size_t)m->np_max * sizeof(double));
+        hipError_t e = m->jrhs.alloc(m->np_max);
         if (e == hipSuccess) return DNAGPU_OK;
         (void)hipGetLastError();
         return fail(ctx, e == hipErrorOutOfMemory ? DNAGPU_ENOMEM : DNAGPU_EHIP, "chain_plan_create: junction right-hand side", e);
@@ -3093,15 +2930,15 @@ int dnagpu_chain_plan_create(dnagpu_ctx* ctx, size_t n_steps, const dnagpu_chain
         }
     }
     {
-        hipError_t e = dnagpu::poison_malloc(&plan->blob, blob.size() + 16);
-        if (e == hipSuccess && plan->keeps) e = dnagpu::poison_malloc(&plan->factors, (size_t)factor_bytes + 16);
-        if (e == hipSuccess) e = dnagpu::poison_malloc(&plan->table, n_steps * sizeof(CbStep));
+        hipError_t e = plan->blob.alloc(blob.size() + 16);
+        if (e == hipSuccess && plan->keeps) e = plan->factors.alloc((size_t)(factor_bytes / 8.0) + 2);
+        if (e == hipSuccess) e = plan->table.alloc(n_steps);
         if (e != hipSuccess) {      // (nothing half allocated stays behind: the caller runs the chains step by step and needs the memory for that)
             (void)hipGetLastError();
             return fail(ctx, e == hipErrorOutOfMemory ? DNAGPU_ENOMEM : DNAGPU_EHIP, "chain_plan_create: device allocation", e);
         }
     }
-    uint8_t* base = (uint8_t*)plan->blob;
+    uint8_t* base = plan->blob;
     for (size_t s = 0; s < n_steps; ++s) {
         CbStep& d = table[s];
         const Offs& o = offs[s];
@@ -3139,17 +2976,10 @@ int dnagpu_chain_plan_run(dnagpu_ctx* ctx, int chain, dnagpu_chain_plan* plan, s
     InvWorkspace& ws = ctx->ws[chain];
     hipStream_t st = ctx->stream[chain];
     gemm_profile_close(ws);
-    const CbStep* table = (const CbStep*)plan->table + first;
+    const CbStep* table = plan->table + first;
     const size_t wspan = ((size_t)batch_panel_cols(sh.nip, sh.njp) + 128) * sh.npp, msq = (size_t)sh.npp * sh.npp;
     const size_t per = msq + wspan + (plan->keeps ? 0 : msq);
-    if (ctx->plan_scratch_cap[chain] < (size_t)nb * per) {
-        HIPCHK(hipStreamSynchronize(st));
-        if (ctx->plan_scratch[chain]) hipFree(ctx->plan_scratch[chain]);
-        ctx->plan_scratch[chain] = nullptr;
-        ctx->plan_scratch_cap[chain] = 0;
-        HIPCHK(dnagpu::poison_malloc(&ctx->plan_scratch[chain], (size_t)nb * per * sizeof(double)));
-        ctx->plan_scratch_cap[chain] = (size_t)nb * per;
-    }
+    HIPCHK(ctx->plan_scratch[chain].grow((size_t)nb * per, 0, {st}));
     CbMembers mem{};
     double* F[BATCH_MAX];
     double* X[BATCH_MAX];
@@ -3320,7 +3150,7 @@ int dnagpu_block_form_reduce_batched(dnagpu_ctx* ctx, int chain, int nb, const u
     hipStream_t st = ctx->stream[chain];
     gemm_profile_close(ws);
     // every member's normals formed in its elimination order, in its own matrix: one launch per kernel for all members (their lists of
-    // constraints must have device copies of their own -- the cache of stage_u32 / stage_f64 --, else one member at a time as before)
+    // constraints must have device copies of their own -- the cache of stage() --, else one member at a time as before)
     FormBatch fb{};
     bool merged = true;
     for (int b = 0; b < nb; ++b) {
@@ -3339,8 +3169,8 @@ int dnagpu_block_form_reduce_batched(dnagpu_ctx* ctx, int chain, int nb, const u
         uint32_t* dstn = nullptr;
         double* dw = nullptr;
         if (n_con[b] && merged) {
-            rc = stage_u32(ctx, chain, con_stn[b], n_con[b], &dstn);
-            if (!rc) rc = stage_f64(ctx, chain, con_w9[b], n_con[b] * 9, &dw);
+            rc = stage(ctx, chain, con_stn[b], n_con[b], &dstn);
+            if (!rc) rc = stage(ctx, chain, con_w9[b], n_con[b] * 9, &dw);
             if (rc) return rc;
             if (dstn == ctx->scr_u32[chain] || dw == ctx->scr_f64[chain]) merged = false;
         }
@@ -3375,8 +3205,8 @@ int dnagpu_block_form_reduce_batched(dnagpu_ctx* ctx, int chain, int nb, const u
         uint32_t* dstn = nullptr;
         double* dw = nullptr;
         if (n_con[b]) {
-            rc = stage_u32(ctx, chain, con_stn[b], n_con[b], &dstn);
-            if (!rc) rc = stage_f64(ctx, chain, con_w9[b], n_con[b] * 9, &dw);
+            rc = stage(ctx, chain, con_stn[b], n_con[b], &dstn);
+            if (!rc) rc = stage(ctx, chain, con_w9[b], n_con[b] * 9, &dw);
             if (rc) return rc;
         }
         Block* B = blk[b];
@@ -3500,7 +3330,7 @@ int dnagpu_block_load_reduced(dnagpu_ctx* ctx, int chain, uint32_t rblk, uint32_
         if (idx_keep[i] >= sb->n_stn) return fail(ctx, DNAGPU_EINVAL, "block_load_reduced: station out of range");
     hipStream_t st = ctx->stream[chain];
     uint32_t* didx = nullptr;
-    int rc = stage_u32(ctx, chain, idx_keep, k, &didx);
+    int rc = stage(ctx, chain, idx_keep, k, &didx);
     if (rc) return rc;
     if (m) {      // (m = NULL: right-hand side and linearisation point only -- a step whose factor is kept, dnagpu_schur_carry_rhs)
         m->n = red->n;
@@ -3520,7 +3350,7 @@ int dnagpu_junction_scatter(dnagpu_ctx* ctx, int chain, dnagpu_matrix* dst, cons
         if (3 * (uint64_t)idx_to[i] + 2 >= dst->n) return fail(ctx, DNAGPU_EINVAL, "junction_scatter: station out of range");
     if (!k) return DNAGPU_OK;
     uint32_t* didx = nullptr;
-    int rc = stage_u32(ctx, chain, idx_to, k, &didx);
+    int rc = stage(ctx, chain, idx_to, k, &didx);
     if (rc) return rc;
     launch_junction_scatter(dst->F, dst->np, didx, (uint32_t)k, jm->F, jm->np, ctx->stream[chain]);
     return DNAGPU_OK;
@@ -3535,7 +3365,7 @@ int dnagpu_junction_rhs(dnagpu_ctx* ctx, int chain, uint32_t blk_to, const uint3
         if (idx_to[i] >= b->n_stn) return fail(ctx, DNAGPU_EINVAL, "junction_rhs: station out of range");
     if (!k) return DNAGPU_OK;
     uint32_t* didx = nullptr;
-    int rc = stage_u32(ctx, chain, idx_to, k, &didx);
+    int rc = stage(ctx, chain, idx_to, k, &didx);
     if (rc) return rc;
     launch_junction_rhs(b->rhs[chain], b->x_est[chain], didx, (uint32_t)k, jm->F, jm->np, jm->jest, jm->form == 1 ? jm->jrhs : nullptr,
                         ctx->stream[chain]);
@@ -3552,7 +3382,7 @@ int dnagpu_block_add_rhs(dnagpu_ctx* ctx, int chain, uint32_t blk, const uint32_
     if (zero_first) HIPCHK(hipMemsetAsync(b->rhs[chain], 0, (size_t)3 * b->n_stn * sizeof(double), ctx->stream[chain]));
     if (!k) return DNAGPU_OK;
     uint32_t* didx = nullptr;
-    int rc = stage_u32(ctx, chain, idx, k, &didx);
+    int rc = stage(ctx, chain, idx, k, &didx);
     if (rc) return rc;
     launch_scatter_add_vec3(b->rhs[chain], didx, (uint32_t)k, jm->jest, ctx->stream[chain]);
     return DNAGPU_OK;
@@ -3571,7 +3401,7 @@ int dnagpu_block_gather_stations(dnagpu_ctx* ctx, int chain, uint32_t dst_blk, c
     std::vector<uint32_t> both(dst_pos, dst_pos + k);
     both.insert(both.end(), src_idx, src_idx + k);
     uint32_t* didx = nullptr;
-    int rc = stage_u32(ctx, chain, both.data(), 2 * k, &didx);
+    int rc = stage(ctx, chain, both.data(), 2 * k, &didx);
     if (rc) return rc;
     launch_copy_vec3_indexed(d->x_est[chain], didx, sb->x_orig, didx + k, (uint32_t)k, ctx->stream[chain]);
     return DNAGPU_OK;
@@ -3607,10 +3437,10 @@ extern "C" int dnagpu_bench_gemm(dnagpu_ctx* ctx, int variant, int mt, int nt, i
     size_t M = (size_t)mt * 128, N = (size_t)nt * 128;
     size_t ld = std::max(std::max(M, N), (size_t)K);
     size_t cols = ld;
-    double *A = nullptr, *B = nullptr, *Cc = nullptr;
-    HIPCHK(dnagpu::poison_malloc(&A, ld * cols * sizeof(double)));
-    HIPCHK(dnagpu::poison_malloc(&B, ld * cols * sizeof(double)));
-    HIPCHK(dnagpu::poison_malloc(&Cc, ld * cols * sizeof(double)));
+    DevBuf<double> A, B, Cc;
+    HIPCHK(A.alloc(ld * cols));
+    HIPCHK(B.alloc(ld * cols));
+    HIPCHK(Cc.alloc(ld * cols));
     // pseudo-random fill (full-range mantissas: zero fill would flatter the clocks)
     std::vector<double> h(ld * 1024);
     uint64_t s = 88172645463325252ull;
@@ -3642,7 +3472,6 @@ extern "C" int dnagpu_bench_gemm(dnagpu_ctx* ctx, int variant, int mt, int nt, i
     hipEventElapsedTime(&ms, e0, e1);
     hipEventDestroy(e0);
     hipEventDestroy(e1);
-    hipFree(A); hipFree(B); hipFree(Cc);
     if (e != hipSuccess) return fail(ctx, DNAGPU_EHIP, "bench_gemm", e);
     if (avg_ms) *avg_ms = ms / reps;
     if (flops) {

@@ -10,6 +10,7 @@
 #include <set>
 #include <utility>
 #include <vector>
+#include "dev_buf.h"
 #include "la_kernels.h"
 
 namespace dnagpu {
@@ -45,15 +46,15 @@ struct InvBatch {
 
 // Workspace shared by every inverse run on one stream ("chain").
 struct InvWorkspace {
-    double* X = nullptr;     // np_cap^2 : L^-1
-    double* W = nullptr;     // np_cap^2 : L21 panels
-    double* svec = nullptr;  // np_cap   : diagonal scaling
-    int* info = nullptr;     // device ints (dpotrf-style info, 0 = ok), one per member of a batched call (BATCH_MAX)
-    int* info_host = nullptr;  // pinned host copy
+    DevBuf<double> X;        // np_cap^2 : L^-1
+    DevBuf<double> W;        // np_cap^2 : L21 panels
+    DevBuf<double> svec;     // np_cap   : diagonal scaling
+    DevBuf<int> info;        // device ints (dpotrf-style info, 0 = ok), one per member of a batched call (BATCH_MAX)
+    HostBuf<int> info_host;  // pinned host copy
     bool hold_info = false;    // dnagpu_chain_hold_info: the drivers leave `info` alone (the first failure of a run of calls stays in it)
     InvBatch batch;          // nb > 1: the call being enqueued is batched
-    double* bX[BATCH_MAX] = {};   // members 1 .. of a batched call: their matrix being factored (bnp_cap^2) ...
-    double* bW[BATCH_MAX] = {};   // ... and the panels inside a diagonal block (bw_cols x bnp_cap)
+    DevBuf<double> bX[BATCH_MAX];   // members 1 .. of a batched call: their matrix being factored (bnp_cap^2) ...
+    DevBuf<double> bW[BATCH_MAX];   // ... and the panels inside a diagonal block (bw_cols x bnp_cap)
     uint32_t bnp_cap = 0, bw_cols = 0;
     uint64_t batched_launches = 0;
     uint32_t np_cap = 0;
@@ -73,8 +74,7 @@ struct InvWorkspace {
     int dist_rank = 0, dist_world = 1;
     int (*exchange)(void* user, void* stream, int nparts, double* const* bufs, const size_t* counts) = nullptr;
     void* exchange_user = nullptr;
-    double* dist_stage = nullptr;
-    size_t dist_stage_cap = 0;
+    DevBuf<double> dist_stage;
     uint64_t split_launches = 0;
     double exchanged_bytes = 0.0;
 };

@@ -15,32 +15,22 @@ namespace dnagpu {
 hipError_t inv_workspace_alloc(InvWorkspace& ws, uint32_t np_cap, hipStream_t stream) {
     ws.np_cap = np_cap;
     ws.stream = stream;
-    size_t bytes = (size_t)np_cap * np_cap * sizeof(double);
+    const size_t count = (size_t)np_cap * np_cap;
     hipError_t e;
-    if ((e = dnagpu::poison_malloc(&ws.X, bytes)) != hipSuccess) return e;
-    if ((e = dnagpu::poison_malloc(&ws.W, bytes)) != hipSuccess) return e;
-    if ((e = dnagpu::poison_malloc(&ws.svec, (size_t)np_cap * sizeof(double))) != hipSuccess) return e;
-    if ((e = dnagpu::poison_malloc(&ws.info, BATCH_MAX * sizeof(int))) != hipSuccess) return e;
-    if ((e = hipHostMalloc(&ws.info_host, BATCH_MAX * sizeof(int))) != hipSuccess) return e;
+    if ((e = ws.X.alloc(count)) != hipSuccess) return e;
+    if ((e = ws.W.alloc(count)) != hipSuccess) return e;
+    if ((e = ws.svec.alloc(np_cap)) != hipSuccess) return e;
+    if ((e = ws.info.alloc(BATCH_MAX)) != hipSuccess) return e;
+    if ((e = ws.info_host.alloc(BATCH_MAX)) != hipSuccess) return e;
     for (int b = 0; b < BATCH_MAX; ++b) ws.info_host[b] = 0;
     return hipSuccess;
 }
 
 void inv_workspace_free(InvWorkspace& ws) {
-    if (ws.X) hipFree(ws.X);
-    if (ws.W) hipFree(ws.W);
-    for (int b = 0; b < BATCH_MAX; ++b) {
-        if (ws.bX[b]) hipFree(ws.bX[b]);
-        if (ws.bW[b]) hipFree(ws.bW[b]);
-    }
-    if (ws.svec) hipFree(ws.svec);
-    if (ws.info) hipFree(ws.info);
-    if (ws.dist_stage) hipFree(ws.dist_stage);
-    if (ws.info_host) hipHostFree(ws.info_host);
     for (hipEvent_t ev : ws.prof.pool) hipEventDestroy(ev);
     for (auto& kv : ws.order_cache)
         if (kv.second.first) hipFree(kv.second.first);
-    ws = InvWorkspace();
+    ws = InvWorkspace();        // (the buffers are freed by the assignment)
 }
 
 void inv_note_error(InvWorkspace& ws, hipError_t e, const char* where) {
@@ -181,19 +171,11 @@ static bool gemm_split(InvWorkspace& ws, GemmArgs a, int akc, int bkc) {
         counts[q] = rows[q] * cols[q];
         off[q + 1] = off[q] + counts[q];
     }
-    if (ws.dist_stage_cap < off[W]) {
-        hipStreamSynchronize(ws.stream);
-        if (ws.dist_stage) hipFree(ws.dist_stage);
-        ws.dist_stage = nullptr;
-        ws.dist_stage_cap = 0;
-        const size_t want = std::max(off[W], (size_t)ws.np_cap * ws.np_cap);
-        hipError_t e = dnagpu::poison_malloc(&ws.dist_stage, want * sizeof(double));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            inv_note_error(ws, e, "staging buffer of the distributed inverse");
-            return true;
-        }
-        ws.dist_stage_cap = want;
+    hipError_t e = ws.dist_stage.grow(off[W], (size_t)ws.np_cap * ws.np_cap, {ws.stream});
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        inv_note_error(ws, e, "staging buffer of the distributed inverse");
+        return true;
     }
     if (ws.err != hipSuccess) return true;
     if (lo[me + 1] > lo[me]) {
