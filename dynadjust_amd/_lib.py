@@ -35,7 +35,8 @@ class DnaAdjSettings(C.Structure):
                 ("scale_normals_to_unity", C.c_int), ("device", C.c_int), ("confidence_interval", C.c_float),
                 ("output_tstat", C.c_int), ("network_name", C.c_char_p), ("output_folder", C.c_char_p), ("reuse_inverses", C.c_int), ("schur_carry", C.c_int), ("stage", C.c_int), ("keep_factors", C.c_int),
                 ("dist_rank", C.c_int), ("dist_world", C.c_int), ("n_devices", C.c_int), ("devices", C.POINTER(C.c_int)),
-                ("dist_transport", C.c_char_p), ("dist_two_level", C.c_int), ("defer_variances", C.c_int), ("batch_blocks", C.c_int), ("reuse_factors", C.c_int), ("chain_runs", C.c_int)]
+                ("dist_transport", C.c_char_p), ("dist_two_level", C.c_int), ("defer_variances", C.c_int), ("batch_blocks", C.c_int), ("reuse_factors", C.c_int), ("chain_runs", C.c_int),
+                ("output_pos_uncertainty", C.c_int), ("output_rel_uncertainty", C.c_int)]
 
 
 class DnaAdjStatistics(C.Structure):
@@ -51,6 +52,12 @@ class DnaAdjInstanceStats(C.Structure):
     _fields_ = [("rank", C.c_int), ("device", C.c_int), ("rccl_ranks", C.c_int), ("solves", C.c_uint32), ("eliminations", C.c_uint32),
                 ("completions", C.c_uint32), ("algorithmic_flops", C.c_double), ("solve_flops", C.c_double), ("exchanged_bytes", C.c_uint64),
                 ("exchange_ms", C.c_double), ("chain_ms", C.c_double)]
+
+
+class DnaGpuUncertainty(C.Structure):
+    """dnagpu_uncertainty (include/dnagpu.h)"""
+    _fields_ = [("enu", C.c_double * 6), ("semi_major", C.c_double), ("semi_minor", C.c_double), ("azimuth", C.c_double),
+                ("hz_pu", C.c_double), ("vt_pu", C.c_double)]
 
 
 class DnaSynthSpec(C.Structure):
@@ -260,6 +267,15 @@ def load():
     _sig(lib, "dnaadj_measurement_records", i, [vp, vp, u64])
     _sig(lib, "dnaadj_block_prec_adj_msrs_count", u64, [vp, u32])
     _sig(lib, "dnaadj_block_prec_adj_msrs", i, [vp, u32, c_f64p, u64])
+    unp = C.POINTER(DnaGpuUncertainty)
+    i32p = C.POINTER(C.c_int32)
+    _sig(lib, "dnagpu_block_station_uncertainty", i, [vp, i, u32, vp, c_u32p, c_f64p, u32, unp])
+    _sig(lib, "dnagpu_block_pair_uncertainty", i, [vp, i, u32, vp, c_u32p, c_f64p, u32, unp])
+    _sig(lib, "dnagpu_debug_uncertainty_3x3", None, [c_f64p, C.c_double, C.c_double, unp])
+    _sig(lib, "dnaadj_positional_uncertainty", i, [vp, unp, i32p, u64, C.POINTER(u64)])
+    _sig(lib, "dnaadj_measured_pairs", i, [vp, c_u32p, u64, C.POINTER(u64)])
+    _sig(lib, "dnaadj_relative_uncertainty", i, [vp, c_u32p, u64, unp, i32p])
+    _sig(lib, "dnaadj_print_positional_uncertainty", i, [vp])
     _sig(lib, "dnaadj_serialise_adjusted_variance_matrices", i, [vp])
     _sig(lib, "dnaadj_deserialise_adjusted_variance_matrices", i, [vp])
     _sig(lib, "dnaadj_update_binary_files", i, [vp])
@@ -328,7 +344,7 @@ EXPORTED_DNAGPU = [
     "dnagpu_matrix_upload_packed", "dnagpu_matrix_download_packed", "dnagpu_matrix_download_packed_async", "dnagpu_copies_sync", "dnagpu_matrix_copy", "dnagpu_matrix_export", "dnagpu_matrix_import", "dnagpu_invert",
     "dnagpu_block_create", "dnagpu_block_destroy", "dnagpu_block_set_stations", "dnagpu_block_reset_stations", "dnagpu_chain_hold_info", "dnagpu_chain_take_info", "dnagpu_block_table_create", "dnagpu_block_table_apply", "dnagpu_block_table_destroy", "dnagpu_block_set_baselines", "dnagpu_block_set_clusters",
     "dnagpu_block_get_stations", "dnagpu_block_put_stations", "dnagpu_block_copy_stations", "dnagpu_block_compute_b",
-    "dnagpu_block_get_b", "dnagpu_block_get_weights", "dnagpu_block_msr_statistics", "dnagpu_block_set_station_geo", "dnagpu_block_set_terrestrial",
+    "dnagpu_block_get_b", "dnagpu_block_get_weights", "dnagpu_block_msr_statistics", "dnagpu_block_station_uncertainty", "dnagpu_block_pair_uncertainty", "dnagpu_debug_uncertainty_3x3", "dnagpu_block_set_station_geo", "dnagpu_block_set_terrestrial",
     "dnagpu_block_set_direction_sets", "dnagpu_block_update_geodetic", "dnagpu_block_get_station_llh", "dnagpu_block_get_terrestrial", "dnagpu_block_terrestrial_precisions", "dnagpu_form_normals", "dnagpu_add_diag3x3", "dnagpu_form_rhs",
     "dnagpu_solve_corrections", "dnagpu_update_estimates", "dnagpu_block_get_corrections", "dnagpu_block_get_rhs",
     "dnagpu_block_add_rhs", "dnagpu_block_gather_stations", "dnagpu_junction_gather", "dnagpu_schur_carry", "dnagpu_schur_carry_keep", "dnagpu_schur_carry_rhs", "dnagpu_chain_step_rhs", "dnagpu_small_batch_create", "dnagpu_small_batch_condense", "dnagpu_small_batch_solve", "dnagpu_small_batch_destroy", "dnagpu_junction_export", "dnagpu_junction_import", "dnagpu_junction_device_pointers", "dnagpu_block_reduce", "dnagpu_block_form_reduce", "dnagpu_batch_reserve", "dnagpu_block_form_reduce_batched", "dnagpu_partial_complete_factor_batched", "dnagpu_partial_finish_batched", "dnagpu_mem_info", "dnagpu_device_alloc", "dnagpu_device_free", "dnagpu_copy", "dnagpu_matrix_resize", "dnagpu_matrix_device_pointers", "dnagpu_set_inverse_exchange", "dnagpu_inverse_exchange_stats", "dnagpu_host_alloc", "dnagpu_host_free", "dnagpu_partial_create", "dnagpu_partial_create_in", "dnagpu_partial_create_spine", "dnagpu_partial_destroy", "dnagpu_partial_complete", "dnagpu_partial_complete_factor", "dnagpu_partial_solve", "dnagpu_partial_finish", "dnagpu_partial_reduce_rhs",
@@ -346,7 +362,8 @@ EXPORTED_DNAADJ = [
     "dnaimport_text", "dnaimport_text_geo", "dnaadj_dist_rccl_available", "dnaadj_dist_unique_id", "dnaadj_dist_attach_rccl", "dnaadj_adjust_distributed", "dnaadj_dist_info",
     "dnaadj_block_owner", "dnaadj_exchange_stats", "dnaadj_device_instance_context", "dnaadj_device_instance_stats", "dnaadj_debug_cancel_instance", "dnaadj_debug_tcp_share_unique_id",
     "dnaadj_generate_statistics", "dnaadj_get_statistics", "dnaadj_measurement_record_count", "dnaadj_measurement_records",
-    "dnaadj_block_prec_adj_msrs_count", "dnaadj_block_prec_adj_msrs", "dnaadj_serialise_adjusted_variance_matrices",
+    "dnaadj_block_prec_adj_msrs_count", "dnaadj_block_prec_adj_msrs", "dnaadj_positional_uncertainty", "dnaadj_measured_pairs",
+    "dnaadj_relative_uncertainty", "dnaadj_print_positional_uncertainty", "dnaadj_serialise_adjusted_variance_matrices",
     "dnaadj_deserialise_adjusted_variance_matrices", "dnaadj_update_binary_files", "dnastat_normal_quantile", "dnastat_chi_squared_quantile",
     "dnaadj_block_flags", "dnaadj_junction_unknowns", "dnaadj_junction_payload_doubles", "dnaadj_phased_begin_iteration",
     "dnaadj_phased_forward_block", "dnaadj_phased_reverse_block", "dnaadj_phased_combine_block", "dnaadj_phased_finalise_block",

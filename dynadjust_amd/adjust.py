@@ -24,6 +24,21 @@ ADJUST_EXCEPTION_RAISED = 5
 ADJUST_CANCELLED = 6
 
 
+UNCERTAINTY_DTYPE = np.dtype([("enu", np.float64, (6,)), ("semi_major", np.float64), ("semi_minor", np.float64), ("azimuth", np.float64),
+                              ("hz_pu", np.float64), ("vt_pu", np.float64), ("block", np.int32)])
+RELATIVE_UNCERTAINTY_DTYPE = np.dtype([("stn1", np.uint32), ("stn2", np.uint32)] + UNCERTAINTY_DTYPE.descr)
+
+
+def _uncertainty_records(rec, blk, n, dtype=UNCERTAINTY_DTYPE):
+    raw = np.frombuffer(rec, dtype=np.float64, count=11 * n).reshape(n, 11)
+    out = np.zeros(n, dtype=dtype)
+    out["enu"] = raw[:, :6]
+    for q, f in enumerate(("semi_major", "semi_minor", "azimuth", "hz_pu", "vt_pu")):
+        out[f] = raw[:, 6 + q]
+    out["block"] = blk[:n]
+    return out
+
+
 class NetAdjustException(RuntimeError):
     """std::runtime_error thrown by dna_adjust::SignalExceptionAdjustment (dnaadjust.cpp:10049)."""
 
@@ -35,12 +50,15 @@ class ProjectSettings:
                  max_iterations=10, iteration_threshold=0.0005, free_std_dev=10.0, fixed_std_dev=1e-6,
                  scale_normals_to_unity=False, device=0, confidence_interval=95.0, output_tstat=False, output_folder=None,
                  reuse_inverses=False, schur_carry=True, keep_factors=True, stage=False, dist_rank=0, dist_world=1, devices=None,
-                 dist_transport=None, dist_two_level=True, defer_variances=2, batch_blocks=32, reuse_factors=True, chain_runs=-1):
+                 dist_transport=None, dist_two_level=True, defer_variances=2, batch_blocks=32, reuse_factors=True, chain_runs=-1,
+                 output_pos_uncertainty=False, output_rel_uncertainty=False):
         self.bst_file = self.bms_file = self.asl_file = self.seg_file = None
         self.network_name = network_name          # g.network_name
         self.output_folder = output_folder if output_folder is not None else folder   # g.output_folder
         self.confidence_interval = confidence_interval
         self.output_tstat = output_tstat          # o._adj_msr_tstat
+        self.output_pos_uncertainty = output_pos_uncertainty   # o._positional_uncertainty: ellipses and hz / vt PU in the .apu report
+        self.output_rel_uncertainty = output_rel_uncertainty   # o._relative_uncertainty: ... and the same for the measured station pairs
         self.reuse_inverses = reuse_inverses      # device path only: block inverses stay resident across iterations
         self.schur_carry = schur_carry            # device path only: carry-only steps eliminate instead of inverting
         self.stage = stage                        # a.stage: rigorous variances in page-locked host memory
@@ -146,6 +164,8 @@ class DnaAdjust:
         s.batch_blocks = int(getattr(p, "batch_blocks", 32))
         s.reuse_factors = int(bool(getattr(p, "reuse_factors", True)))
         s.chain_runs = int(getattr(p, "chain_runs", -1))
+        s.output_pos_uncertainty = int(bool(getattr(p, "output_pos_uncertainty", False)))
+        s.output_rel_uncertainty = int(bool(getattr(p, "output_rel_uncertainty", False)))
         return s
 
     # ---- multi-GPU (include/dnaadjust_c.h "multi-GPU") ----
@@ -280,6 +300,42 @@ class DnaAdjust:
         if n:
             self._chk(self.lib.dnaadj_block_prec_adj_msrs(self.h, block, out.ctypes.data_as(c_f64p), n))
         return out
+
+    # ---- positional and relative uncertainty (include/dnaadjust_c.h; records: UNCERTAINTY_DTYPE) ----
+    def GetPositionalUncertainty(self):
+        """one record per .bst station: enu (ee en eu nn nu uu), semi_major, semi_minor, azimuth, hz_pu, vt_pu and block
+        (the block it was computed in, -1 = none)"""
+        n = C.c_uint64(0)
+        self._chk(self.lib.dnaadj_positional_uncertainty(self.h, None, None, 0, C.byref(n)))
+        rec = (_lib.DnaGpuUncertainty * max(n.value, 1))()
+        blk = np.full(max(n.value, 1), -1, dtype=np.int32)
+        self._chk(self.lib.dnaadj_positional_uncertainty(self.h, rec, blk.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(n)))
+        return _uncertainty_records(rec, blk, n.value)
+
+    def measured_pairs(self):
+        """the distinct station pairs joined by a measurement that is not ignored, (k, 2) global station indices"""
+        n = C.c_uint64(0)
+        self._chk(self.lib.dnaadj_measured_pairs(self.h, None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 2), dtype=np.uint32)
+        self._chk(self.lib.dnaadj_measured_pairs(self.h, out.ctypes.data_as(c_u32p), n.value, C.byref(n)))
+        return out[:n.value]
+
+    def GetRelativeUncertainty(self, pairs=None):
+        """the vector between the stations of each pair (global station indices; None = measured_pairs()) in the local frame of its
+        first station: the fields of GetPositionalUncertainty plus stn1, stn2; block = -1 where no block holds both stations"""
+        pairs = self.measured_pairs() if pairs is None else np.ascontiguousarray(np.asarray(pairs, dtype=np.uint32).reshape(-1, 2))
+        n = len(pairs)
+        rec = (_lib.DnaGpuUncertainty * max(n, 1))()
+        blk = np.full(max(n, 1), -1, dtype=np.int32)
+        self._chk(self.lib.dnaadj_relative_uncertainty(self.h, pairs.ctypes.data_as(c_u32p), n, rec,
+                                                       blk.ctypes.data_as(C.POINTER(C.c_int32))))
+        out = _uncertainty_records(rec, blk, n, RELATIVE_UNCERTAINTY_DTYPE)
+        out["stn1"], out["stn2"] = pairs[:, 0], pairs[:, 1]
+        return out
+
+    def PrintPositionalUncertainty(self):
+        """GetPrinter()->PrintPositionalUncertainty(): <output_folder>/<network_name>.<simult|phased>.apu"""
+        self._chk(self.lib.dnaadj_print_positional_uncertainty(self.h))
 
     def block_stations(self, block):
         n = self.lib.dnaadj_block_station_count(self.h, block)

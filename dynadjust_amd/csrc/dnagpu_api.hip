@@ -14,6 +14,7 @@
 #include "la_kernels.h"
 #include "terrestrial.h"
 #include "sym_inverse.h"
+#include "uncertainty.h"
 
 using namespace dnagpu;
 
@@ -1665,6 +1666,47 @@ int dnagpu_block_msr_statistics(dnagpu_ctx* ctx, int chain, uint32_t blk, const 
         HIPCHK(hipMemcpyAsync(prec6, dprec, (size_t)b->n_bl * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream[chain]));
     }
     return d2h(ctx, chain, chi, dchi, (size_t)b->n_bl * sizeof(double));
+}
+
+// dnagpu_block_station_uncertainty (per = 1 index per entry) and dnagpu_block_pair_uncertainty (per = 2): the indices are checked here,
+// on the host, so that the kernels never read outside the block's variance matrix
+static int block_uncertainty(dnagpu_ctx* ctx, int chain, uint32_t blk, const dnagpu_matrix* variances, const uint32_t* idx, int per,
+                             const double* latlon, uint32_t count, dnagpu_uncertainty* out, const char* what) {
+    CHK_CTX();
+    CHK_CHAIN();
+    Block* b = find_block(ctx, blk);
+    if (!b || !variances || variances->n != 3 * b->n_stn || (count && (!idx || !latlon || !out)))
+        return fail(ctx, DNAGPU_EINVAL, what);
+    const size_t ni = (size_t)per * count;
+    for (size_t k = 0; k < ni; ++k)
+        if (idx[k] >= b->n_stn) return fail(ctx, DNAGPU_EINVAL, what);
+    if (!count) return DNAGPU_OK;
+    hipStream_t st = ctx->stream[chain];
+    HIPCHK(ctx->scr_u32[chain].grow(ni, 4096, {st}));
+    int rc = ensure_scr_f64(ctx, chain, (size_t)(2 + un::RECORD_DOUBLES) * count);
+    if (rc) return rc;
+    double* dll = ctx->scr_f64[chain];
+    double* dout = dll + 2 * (size_t)count;
+    HIPCHK(hipMemcpyAsync(ctx->scr_u32[chain], idx, ni * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dll, latlon, 2 * (size_t)count * sizeof(double), hipMemcpyHostToDevice, st));
+    if (per == 1)
+        launch_station_uncertainty(variances->F, variances->np, ctx->scr_u32[chain], dll, dout, count, st);
+    else
+        launch_pair_uncertainty(variances->F, variances->np, ctx->scr_u32[chain], dll, dout, count, st);
+    HIPCHK(hipGetLastError());
+    return d2h(ctx, chain, out, dout, (size_t)count * sizeof(dnagpu_uncertainty));
+}
+
+int dnagpu_block_station_uncertainty(dnagpu_ctx* ctx, int chain, uint32_t blk, const dnagpu_matrix* variances, const uint32_t* local_stn,
+                                     const double* latlon, uint32_t count, dnagpu_uncertainty* out) {
+    return block_uncertainty(ctx, chain, blk, variances, local_stn, 1, latlon, count, out,
+                             "block_station_uncertainty: bad arguments or station index out of range");
+}
+
+int dnagpu_block_pair_uncertainty(dnagpu_ctx* ctx, int chain, uint32_t blk, const dnagpu_matrix* variances, const uint32_t* local_pairs,
+                                  const double* latlon_first, uint32_t count, dnagpu_uncertainty* out) {
+    return block_uncertainty(ctx, chain, blk, variances, local_pairs, 2, latlon_first, count, out,
+                             "block_pair_uncertainty: bad arguments or station index out of range");
 }
 
 int dnagpu_block_get_corrections(dnagpu_ctx* ctx, int chain, uint32_t blk, double* corr) {

@@ -1123,6 +1123,146 @@ void dna_adjust::GetAdjustedCoordinates(std::vector<double>& xyz) {
     }
 }
 
+// ---- positional and relative uncertainty ----------------------------------------------------------------------------------------
+
+bool dna_adjust::BlockUncertainty(UINT32 b, const std::vector<UINT32>& stn, const std::vector<UINT32>& pairs, dnagpu_uncertainty* pu,
+                                  dnagpu_uncertainty* ru) {
+    if (!peers_.empty() && !OwnsBlock(b))     // another GPU of this process holds it
+        return DeviceInstance(BlockOwner(b))->BlockUncertainty(b, stn, pairs, pu, ru);
+    if (Distributed() && !OwnsBlock(b)) return false;
+    dnagpu_matrix* var = BlockVariancesOnDevice(b, "GetPositionalUncertainty()");
+    if (!var) return false;
+    // the frame: geodetic position of the block's rigorous estimate (as DynAdjustPrinter::StationResults)
+    std::vector<double> xyz;
+    GetBlockRigorousStations(b, xyz);
+    auto latlon = [&](const std::vector<UINT32>& idx, size_t stride) {
+        std::vector<double> ll(2 * (idx.size() / stride));
+        for (size_t k = 0; k < ll.size() / 2; ++k) {
+            const double* x = &xyz[3 * (size_t)idx[stride * k]];
+            double h;
+            geodesy::CartToGeo(x[0], x[1], x[2], &ll[2 * k], &ll[2 * k + 1], &h);
+        }
+        return ll;
+    };
+    if (!stn.empty()) {
+        const std::vector<double> ll = latlon(stn, 1);
+        Check(dnagpu_block_station_uncertainty(ctx_, 0, b, var, stn.data(), ll.data(), (uint32_t)stn.size(), pu), b, "GetPositionalUncertainty()");
+    }
+    if (!pairs.empty()) {
+        const std::vector<double> ll = latlon(pairs, 2);
+        Check(dnagpu_block_pair_uncertainty(ctx_, 0, b, var, pairs.data(), ll.data(), (uint32_t)(pairs.size() / 2), ru), b, "GetRelativeUncertainty()");
+    }
+    return true;
+}
+
+void dna_adjust::GetPositionalUncertainty(std::vector<dnagpu_uncertainty>& pu, std::vector<INT32>& block) {
+    if (!ctx_) SignalExceptionAdjustment("GetPositionalUncertainty(): PrepareAdjustment() has not been called.", 0);
+    pu.assign(bstBinaryRecords_.size(), dnagpu_uncertainty{});
+    block.assign(bstBinaryRecords_.size(), -1);
+    std::vector<UINT32> local, global;
+    std::vector<dnagpu_uncertainty> out;
+    for (UINT32 b = 0; b < blockCount_; ++b) {
+        // every station is inner to exactly one block (dnasegment.cpp:529-531)
+        const std::vector<UINT32>& stations = v_parameterStationList_[b];
+        local.clear();
+        global.clear();
+        for (UINT32 s : v_ISL_[b]) {
+            const size_t l = (size_t)(std::lower_bound(stations.begin(), stations.end(), s) - stations.begin());
+            if (l >= stations.size() || stations[l] != s || s >= bstBinaryRecords_.size()) continue;
+            local.push_back((UINT32)l);
+            global.push_back(s);
+        }
+        if (local.empty()) continue;
+        out.assign(local.size(), dnagpu_uncertainty{});
+        if (!BlockUncertainty(b, local, {}, out.data(), nullptr)) continue;
+        for (size_t k = 0; k < global.size(); ++k) {
+            pu[global[k]] = out[k];
+            block[global[k]] = (INT32)b;
+        }
+    }
+}
+
+void dna_adjust::GetRelativeUncertainty(const std::vector<std::pair<UINT32, UINT32>>& stn_pairs, std::vector<dnagpu_uncertainty>& ru,
+                                        std::vector<INT32>& block) {
+    if (!ctx_) SignalExceptionAdjustment("GetRelativeUncertainty(): PrepareAdjustment() has not been called.", 0);
+    ru.assign(stn_pairs.size(), dnagpu_uncertainty{});
+    block.assign(stn_pairs.size(), -1);
+    // the blocks of every station, ascending
+    std::vector<std::vector<UINT32>> blocks_of(bstBinaryRecords_.size());
+    for (UINT32 b = 0; b < blockCount_; ++b)
+        for (UINT32 s : v_parameterStationList_[b])
+            if (s < blocks_of.size()) blocks_of[s].push_back(b);
+    // each pair to the first block that holds both of its stations
+    std::vector<std::vector<UINT32>> local(blockCount_), which(blockCount_);
+    for (size_t k = 0; k < stn_pairs.size(); ++k) {
+        const UINT32 i = stn_pairs[k].first, j = stn_pairs[k].second;
+        if (i >= blocks_of.size() || j >= blocks_of.size()) continue;
+        const std::vector<UINT32>& bi = blocks_of[i];
+        const std::vector<UINT32>& bj = blocks_of[j];
+        auto p = bi.begin();
+        auto q = bj.begin();
+        while (p != bi.end() && q != bj.end() && *p != *q) {
+            if (*p < *q) ++p;
+            else ++q;
+        }
+        if (p == bi.end() || q == bj.end()) continue;
+        const UINT32 b = *p;
+        const std::vector<UINT32>& stations = v_parameterStationList_[b];
+        local[b].push_back((UINT32)(std::lower_bound(stations.begin(), stations.end(), i) - stations.begin()));
+        local[b].push_back((UINT32)(std::lower_bound(stations.begin(), stations.end(), j) - stations.begin()));
+        which[b].push_back((UINT32)k);
+    }
+    std::vector<dnagpu_uncertainty> out;
+    for (UINT32 b = 0; b < blockCount_; ++b) {
+        if (which[b].empty()) continue;
+        out.assign(which[b].size(), dnagpu_uncertainty{});
+        if (!BlockUncertainty(b, {}, local[b], nullptr, out.data())) continue;
+        for (size_t k = 0; k < which[b].size(); ++k) {
+            ru[which[b][k]] = out[k];
+            block[which[b][k]] = (INT32)b;
+        }
+    }
+}
+
+std::vector<std::pair<UINT32, UINT32>> dna_adjust::GetMeasuredStationPairs() const {
+    std::vector<std::pair<UINT32, UINT32>> pairs;
+    std::vector<std::pair<UINT32, UINT32>> seen;     // (min, max) of every pair so far, for the distinct test
+    auto add = [&](UINT32 i, UINT32 j) {
+        if (i == j || i >= bstBinaryRecords_.size() || j >= bstBinaryRecords_.size()) return;
+        pairs.emplace_back(i, j);
+        seen.emplace_back(std::min(i, j), std::max(i, j));
+    };
+    const size_t nm = bmsBinaryRecords_.size();
+    for (size_t m = 0; m < nm; ++m) {
+        const measurement_t& r = bmsBinaryRecords_[m];
+        if (r.ignore) continue;
+        const char type = r.measType;
+        if (type == 'D') {
+            // a direction set: the record of the reference direction (vectorCount1 = records of the set) and the other directions
+            // (CDnaDirectionSet::WriteBinaryMsr); instrument to every target that is not ignored
+            if (r.measStart != 0 || r.vectorCount1 < 1) continue;
+            for (size_t j = m; j < std::min(nm, m + r.vectorCount1); ++j)
+                if (bmsBinaryRecords_[j].measType == 'D' && !bmsBinaryRecords_[j].ignore) add(r.station1, bmsBinaryRecords_[j].station2);
+            continue;
+        }
+        if (r.measStart != 0) continue;           // (the Y, Z and covariance rows of a GNSS vector)
+        if (type == 'Y' || dnagpu::tm::single_station(type)) continue;
+        add(r.station1, r.station2);              // G, every baseline of an X cluster, every two-station type
+        if (type == 'A') add(r.station1, r.station3);
+    }
+    // distinct: the first occurrence of each unordered pair, in record order
+    std::vector<size_t> order(seen.size());
+    for (size_t k = 0; k < order.size(); ++k) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return seen[x] < seen[y]; });
+    std::vector<char> keep(seen.size(), 0);
+    for (size_t k = 0; k < order.size(); ++k)
+        if (k == 0 || seen[order[k]] != seen[order[k - 1]]) keep[order[k]] = 1;
+    std::vector<std::pair<UINT32, UINT32>> out;
+    for (size_t k = 0; k < pairs.size(); ++k)
+        if (keep[k]) out.push_back(pairs[k]);
+    return out;
+}
+
 // the a-priori coordinates of every block, once more in HBM: a reset is then one launch instead of six copies from the host and a launch
 // per chain for every block (113 ms -> 3 ms for the 666 blocks of a default dnasegment cut)
 void dna_adjust::EnsureInitialOnDevice() {
@@ -1270,6 +1410,24 @@ void dna_adjust::StatisticsBegin() {
     record_touched_.assign(bmsBinaryRecords_.size(), 0);
 }
 
+dnagpu_matrix* dna_adjust::BlockVariancesOnDevice(UINT32 b, const char* where) {
+    const bool phased = projectSettings_.a.adjust_mode != SimultaneousMode;
+    block_t& B = blocks_[b];
+    dnagpu_matrix* var = phased ? (B.has_rigvar ? B.rigvar : nullptr) : work_[0];
+    if (phased && Staged() && B.has_rigvar && B.rig_host) {
+        // staged: the block's rigorous variances come back from host memory into the work matrix (lower triangle: all the
+        // statistics kernels read)
+        var = work_[0];
+        const auto t0 = std::chrono::steady_clock::now();
+        if (B.rig_on_device)
+            Check(dnagpu_matrix_unpack_device(ctx_, 0, var, B.rig_host, (UINT32)v_parameterStationList_[b].size() * 3), b, where);
+        else
+            Check(dnagpu_matrix_upload_packed(ctx_, 0, var, B.rig_host, (UINT32)v_parameterStationList_[b].size() * 3), b, where);
+        profileStageLoadNs_ += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return var;
+}
+
 // ... one block: precisions of the adjusted measurements from its rigorous variances, the per-record statistics, its chi-square terms ...
 void dna_adjust::StatisticsBlock(UINT32 b) {
     const bool phased = projectSettings_.a.adjust_mode != SimultaneousMode;
@@ -1278,18 +1436,7 @@ void dna_adjust::StatisticsBlock(UINT32 b) {
     {
         block_t& B = blocks_[b];
         const size_t nv = B.stn1.size();
-        dnagpu_matrix* var = phased ? (B.has_rigvar ? B.rigvar : nullptr) : work_[0];
-        if (phased && Staged() && B.has_rigvar && B.rig_host) {
-            // staged: the block's rigorous variances come back from host memory into the work matrix (lower triangle: all the
-            // statistics kernels read)
-            var = work_[0];
-            const auto t0 = std::chrono::steady_clock::now();
-            if (B.rig_on_device)
-                Check(dnagpu_matrix_unpack_device(ctx_, 0, var, B.rig_host, (UINT32)v_parameterStationList_[b].size() * 3), b, "ComputePrecisionAdjMsrs()");
-            else
-                Check(dnagpu_matrix_upload_packed(ctx_, 0, var, B.rig_host, (UINT32)v_parameterStationList_[b].size() * 3), b, "ComputePrecisionAdjMsrs()");
-            profileStageLoadNs_ += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-        }
+        dnagpu_matrix* var = BlockVariancesOnDevice(b, "ComputePrecisionAdjMsrs()");
         if (!var) SignalExceptionAdjustment("ComputePrecisionAdjMsrs(): this process holds no rigorous variances for the block.", b);
         prec6.assign(6 * nv + 1, 0.0);
         chi.assign(nv + 1, 0.0);

@@ -158,6 +158,25 @@ public:
         return blocks_.at(block).prec_adj_msrs;
     }
 
+    // Positional and relative uncertainty (dnagpu_block_station_uncertainty / _pair_uncertainty: reduced on the device from the rigorous
+    // variance matrices where they sit, nothing of order n^2 crosses the host link).
+    // One entry per .bst station, computed in the block where the station is an inner station (ISL, the rule of
+    // DynAdjustPrinter::StationResults) in the local frame of its adjusted position; block[s] = that block, or -1 (and zeros) for a
+    // station in no block, or in a block this process holds no rigorous variances of.
+    void GetPositionalUncertainty(std::vector<dnagpu_uncertainty>& pu, std::vector<INT32>& block);
+    size_t GetStationRecordCount() const { return bstBinaryRecords_.size(); }   // .bst records (the length of the above)
+    // The vector between two stations (global .bst indices) of each pair, in the local frame of the pair's FIRST station, from the first
+    // block whose parameter station list holds both; block[k] = -1 (and zeros) when no block holds both (phased mode has no covariances
+    // between blocks) or this process holds no rigorous variances of that block.
+    void GetRelativeUncertainty(const std::vector<std::pair<UINT32, UINT32>>& stn_pairs, std::vector<dnagpu_uncertainty>& ru,
+                                std::vector<INT32>& block);
+    // The distinct pairs of stations joined by a measurement that is not ignored: the two stations of a two-station measurement, instrument
+    // and each target of an angle (A) or direction set (D), the two ends of every baseline of a cluster (X); nothing for point clusters
+    // (Y) and single-station types.  Every pair lies in the block that holds its measurement.
+    std::vector<std::pair<UINT32, UINT32>> GetMeasuredStationPairs() const;
+    // (with a.devices a block of another GPU of this process is computed by that GPU's instance; with one process per rank a rank
+    //  computes its own blocks and reports the others as -1 -- the reach of GetBlockRigorousVariancesPacked)
+
     // ---- multi-GPU (not in the reference: its parallel driver is AdjustPhasedMultiThread, dnaadjust-multi.cpp:92-244) ----------
     // One process per GPU: give every process its rank (a.dist_rank / a.dist_world) and either attach a communicator before
     // PrepareAdjustment() or let PrepareAdjustment() make the RCCL one itself (the unique id travels over TCP from rank 0,
@@ -563,6 +582,13 @@ private:
     std::vector<unsigned char> record_touched_;   // records whose statistics this process computed (UpdateMsrRecord)
     std::atomic<bool> chain_failed_{false};
     void OnEveryChain(const std::function<void(int)>& body);
+    // the device matrix that holds block b's rigorous variances (lower triangle): rigvar in phased mode, work_[0] in simultaneous mode,
+    // or -- staged -- the block's packed slot unpacked into work_[0]; nullptr when this instance holds none
+    dnagpu_matrix* BlockVariancesOnDevice(UINT32 b, const char* where);
+    // block b's share of GetPositionalUncertainty / GetRelativeUncertainty (block-local stations; pairs: 2 indices each) on the instance
+    // that holds its rigorous variances; false when this process holds none
+    bool BlockUncertainty(UINT32 b, const std::vector<UINT32>& stn, const std::vector<UINT32>& pairs, dnagpu_uncertainty* pu,
+                          dnagpu_uncertainty* ru);
     void ForBlocks(const std::vector<UINT32>& blocks, const std::function<void(int, UINT32)>& step);
     // a.batch_blocks: blocks of one shape as batches (dnagpu_*_batched).  phase: 0 condensing, 1 rigorous solve, 2 variance matrices
     int BatchCap() const;

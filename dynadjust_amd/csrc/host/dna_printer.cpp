@@ -173,6 +173,50 @@ void DynAdjustPrinter::PrintPositionalUncertainty() {
         for (int k = 0; k < 6; ++k) os << std::setw(16) << r.var[k];
         os << "\n";
     }
+    // o._positional_uncertainty / o._relative_uncertainty (--output-pos-uncertainty): the ICSM SP1 figures, reduced on the device
+    const output_settings& o = a_.projectSettings_.o;
+    if (!o._positional_uncertainty && !o._relative_uncertainty) return;
+    const std::vector<station_t>& bst = a_.bstBinaryRecords_;
+    auto name = [&](UINT32 s) { return std::string(bst[s].stationName, strnlen(bst[s].stationName, sizeof(bst[s].stationName))); };
+    auto row = [&](const dnagpu_uncertainty& u) {
+        os << std::right << std::fixed << std::setprecision(4) << std::setw(11) << u.azimuth * (180.0 / 3.14159265358979323846) << std::setw(11)
+           << u.semi_major << std::setw(11) << u.semi_minor << std::setw(11) << u.hz_pu << std::setw(11) << u.vt_pu << std::scientific
+           << std::setprecision(6);
+        for (int k = 0; k < 6; ++k) os << std::setw(16) << u.enu[k];
+        os << "\n";
+    };
+    auto heading = [&]() {
+        os << std::right << std::setw(11) << "Az(deg)" << std::setw(11) << "Semi-major" << std::setw(11) << "Semi-minor" << std::setw(11) << "Hz PU"
+           << std::setw(11) << "Vt PU" << std::setw(16) << "EE" << std::setw(16) << "EN" << std::setw(16) << "EU" << std::setw(16) << "NN"
+           << std::setw(16) << "NU" << std::setw(16) << "UU" << "\n";
+    };
+    if (o._positional_uncertainty) {
+        std::vector<dnagpu_uncertainty> pu;
+        std::vector<INT32> blk;
+        a_.GetPositionalUncertainty(pu, blk);
+        os << "\nPositional Uncertainty (1-sigma error ellipse, hz / vt PU at 95 % (ICSM SP1), local variances e n up, m^2)\n"
+           << std::left << std::setw(21) << "Station";
+        heading();
+        for (size_t s = 0; s < pu.size(); ++s) {
+            if (blk[s] < 0) continue;
+            os << std::left << std::setw(21) << name((UINT32)s);
+            row(pu[s]);
+        }
+    }
+    if (o._relative_uncertainty) {
+        const std::vector<std::pair<UINT32, UINT32>> pairs = a_.GetMeasuredStationPairs();
+        std::vector<dnagpu_uncertainty> ru;
+        std::vector<INT32> blk;
+        a_.GetRelativeUncertainty(pairs, ru, blk);
+        os << "\nRelative Uncertainty (stations joined by a measurement; in the local frame of station 1, as above)\n"
+           << std::left << std::setw(21) << "Station 1" << std::setw(21) << "Station 2";
+        heading();
+        for (size_t k = 0; k < pairs.size(); ++k) {
+            if (blk[k] < 0) continue;
+            os << std::left << std::setw(21) << name(pairs[k].first) << std::setw(21) << name(pairs[k].second);
+            row(ru[k]);
+        }
+    }
 }
 
 void DynAdjustPrinter::PrintNetworkStationCorrections() {

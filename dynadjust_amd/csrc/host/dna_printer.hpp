@@ -26,7 +26,9 @@ public:
     void PrintAdjustedNetworkMeasurements();     // -> <net>.<mode>.adj : adjusted measurements, corrections, precisions, N-statistics
     void PrintMeasurementsToStation();           // -> <net>.<mode>.adj : measurements per station
     void PrintAdjustedNetworkStations();         // -> <net>.<mode>.adj and .xyz : adjusted coordinates and their standard deviations (e, n, up)
-    void PrintPositionalUncertainty();           // -> <net>.<mode>.apu : 3 x 3 variance matrix per station
+    void PrintPositionalUncertainty();           // -> <net>.<mode>.apu : 3 x 3 variance matrix per station; with o._positional_uncertainty
+                                                 //    also error ellipse, hz / vt PU and local variances per station, with
+                                                 //    o._relative_uncertainty the same for every pair of stations joined by a measurement
     void PrintNetworkStationCorrections();       // -> <net>.<mode>.cor : adjusted minus initial coordinates
     // dnaadjustwrapper.cpp:389-458: the exporters belong to dnaimport's formats (DynaML, DNA, SINEX): not part of this library
     void PrintEstimatedStationCoordinatestoDNAXML(const std::string& file, int type, bool flagUnused = false);

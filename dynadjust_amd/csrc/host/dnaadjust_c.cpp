@@ -106,6 +106,8 @@ static void to_project_settings(const dnaadj_settings* s, dynadjust::project_set
     p.a.chain_runs = s->chain_runs < 0 ? -1 : s->chain_runs > 4096 ? 4096 : s->chain_runs;
     if (s->network_name) p.g.network_name = s->network_name;
     if (s->output_folder) p.g.output_folder = s->output_folder;
+    p.o._positional_uncertainty = (uint16_t)(s->output_pos_uncertainty ? 1 : 0);
+    p.o._relative_uncertainty = (uint16_t)(s->output_rel_uncertainty ? 1 : 0);
 }
 
 int dnaadj_prepare(dnaadj_handle* h, const dnaadj_settings* s) {
@@ -301,6 +303,55 @@ int dnaadj_block_prec_adj_msrs(const dnaadj_handle* h, uint32_t block, double* o
     if (cap < p.size()) return DNAADJ_EINVAL;
     if (!p.empty()) memcpy(out, p.data(), p.size() * sizeof(double));
     return DNAADJ_OK;
+}
+
+int dnaadj_positional_uncertainty(dnaadj_handle* h, dnagpu_uncertainty* pu, int32_t* block, uint64_t cap, uint64_t* n_stations) {
+    if (!h || !h->adj || (!pu) != (!block)) return DNAADJ_EINVAL;
+    const uint64_t n = h->adj->GetStationRecordCount();
+    if (n_stations) *n_stations = n;
+    if (!pu) return DNAADJ_OK;
+    if (cap < n) return DNAADJ_EINVAL;
+    return guarded(h, [&] {
+        std::vector<dnagpu_uncertainty> u;
+        std::vector<dynadjust::INT32> b;
+        h->adj->GetPositionalUncertainty(u, b);
+        if (!u.empty()) {
+            memcpy(pu, u.data(), u.size() * sizeof(u[0]));
+            memcpy(block, b.data(), b.size() * sizeof(b[0]));
+        }
+    });
+}
+
+int dnaadj_measured_pairs(dnaadj_handle* h, uint32_t* pairs, uint64_t cap_pairs, uint64_t* n_pairs) {
+    return guarded(h, [&] {
+        const auto p = h->adj->GetMeasuredStationPairs();
+        if (n_pairs) *n_pairs = p.size();
+        if (!pairs) return;
+        if (cap_pairs < p.size()) throw std::invalid_argument("dnaadj_measured_pairs(): the buffer holds fewer pairs than there are");
+        for (size_t k = 0; k < p.size(); ++k) {
+            pairs[2 * k] = p[k].first;
+            pairs[2 * k + 1] = p[k].second;
+        }
+    });
+}
+
+int dnaadj_relative_uncertainty(dnaadj_handle* h, const uint32_t* pairs, uint64_t n_pairs, dnagpu_uncertainty* ru, int32_t* block) {
+    if (n_pairs && (!pairs || !ru || !block)) return DNAADJ_EINVAL;
+    return guarded(h, [&] {
+        std::vector<std::pair<dynadjust::UINT32, dynadjust::UINT32>> p(n_pairs);
+        for (size_t k = 0; k < n_pairs; ++k) p[k] = {pairs[2 * k], pairs[2 * k + 1]};
+        std::vector<dnagpu_uncertainty> u;
+        std::vector<dynadjust::INT32> b;
+        h->adj->GetRelativeUncertainty(p, u, b);
+        if (!u.empty()) {
+            memcpy(ru, u.data(), u.size() * sizeof(u[0]));
+            memcpy(block, b.data(), b.size() * sizeof(b[0]));
+        }
+    });
+}
+
+int dnaadj_print_positional_uncertainty(dnaadj_handle* h) {
+    return guarded(h, [&] { h->adj->GetPrinter()->PrintPositionalUncertainty(); });
 }
 
 int dnaadj_serialise_adjusted_variance_matrices(dnaadj_handle* h) {

@@ -14,6 +14,7 @@
 namespace dynadjust {
 
 typedef uint32_t UINT32;
+typedef int32_t INT32;
 typedef uint16_t UINT16;
 
 // widths, include/config/dnatypes-basic.hpp:66-76
@@ -251,6 +252,8 @@ struct adjust_settings {
 };
 struct output_settings {
     UINT16 _adj_msr_tstat = 0;   // --output-tstat-adj-msr: Student's t statistic of every adjusted measurement
+    UINT16 _positional_uncertainty = 0;   // --output-pos-uncertainty: the .apu report also lists error ellipses and hz / vt PU per station
+    UINT16 _relative_uncertainty = 0;     // ... and the relative uncertainty of every pair of stations joined by a measurement
 };
 struct project_settings {
     general_settings g;

@@ -15,6 +15,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "dnagpu.h"   /* dnagpu_uncertainty */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -77,6 +79,9 @@ typedef struct {
                                   junction chains are cut into this many runs whose steps advance together in merged launches
                                   (dna_adjust::LockstepChains, dnagpu_chain_plan_*): 2 B / W + W steps deep instead of B.  0 / 1 = one
                                   run (the chains step by step, block after block) */
+    int output_pos_uncertainty;/* o._positional_uncertainty (--output-pos-uncertainty, default 0): the .apu report also lists the error ellipse,
+                                  hz / vt PU and local variances of every station */
+    int output_rel_uncertainty;/* o._relative_uncertainty (default 0): ... and the same for every pair of stations joined by a measurement */
 } dnaadj_settings;
 
 #define DNAADJ_OK 0
@@ -156,6 +161,20 @@ int dnaadj_measurement_records(const dnaadj_handle* h, void* records, uint64_t c
 /* v_precAdjMsrsFull_ of a block: 6 doubles (xx xy xz yy yz zz) per GNSS vector in CML order */
 uint64_t dnaadj_block_prec_adj_msrs_count(const dnaadj_handle* h, uint32_t block);
 int dnaadj_block_prec_adj_msrs(const dnaadj_handle* h, uint32_t block, double* out, uint64_t cap);
+/* Positional and relative uncertainty (dna_adjust::GetPositionalUncertainty / GetRelativeUncertainty / GetMeasuredStationPairs; the
+ * record: include/dnagpu.h dnagpu_uncertainty).  Replace the reference's PU computation in its .apu printer and, here,
+ * DynAdjustPrinter::StationResults' download of every block's whole variance matrix: reduced on the device, O(stations + pairs) out.
+ *   positional: one record per .bst station; block[s] = the block it was computed in (the block where it is an inner station), -1 = none.
+ *               *n_stations receives the count; pu / block may be NULL (count query), else cap >= that count (DNAADJ_EINVAL otherwise).
+ *   measured pairs: the distinct station pairs joined by a measurement that is not ignored, 2 global station indices each; count
+ *               query as above.
+ *   relative:   n_pairs pairs (2 global station indices each) -> ru[k] in the local frame of the pair's first station, block[k] = the
+ *               first block holding both stations, -1 = none (phased mode has no covariance between blocks). */
+int dnaadj_positional_uncertainty(dnaadj_handle* h, dnagpu_uncertainty* pu, int32_t* block, uint64_t cap, uint64_t* n_stations);
+int dnaadj_measured_pairs(dnaadj_handle* h, uint32_t* pairs, uint64_t cap_pairs, uint64_t* n_pairs);
+int dnaadj_relative_uncertainty(dnaadj_handle* h, const uint32_t* pairs, uint64_t n_pairs, dnagpu_uncertainty* ru, int32_t* block);
+/* GetPrinter()->PrintPositionalUncertainty(): <output_folder>/<network_name>.<simult|phased>.apu */
+int dnaadj_print_positional_uncertainty(dnaadj_handle* h);
 int dnaadj_serialise_adjusted_variance_matrices(dnaadj_handle* h);         /* SerialiseAdjustedVarianceMatrices (dnaadjust.cpp:6770) */
 int dnaadj_deserialise_adjusted_variance_matrices(dnaadj_handle* h);       /* DeSerialiseAdjustedVarianceMatrices (dnaadjust.cpp:6720) */
 int dnaadj_update_binary_files(dnaadj_handle* h);                          /* UpdateBinaryFiles (dnaadjust.cpp:445) */

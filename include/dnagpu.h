@@ -282,6 +282,28 @@ int dnagpu_block_get_weights(dnagpu_ctx* ctx, int chain, uint32_t blk, double* w
  *                     3*stations of the block); skipped when `variances` is NULL.  Host buffers. */
 int dnagpu_block_msr_statistics(dnagpu_ctx* ctx, int chain, uint32_t blk, const dnagpu_matrix* variances, double* prec6, double* chi);
 
+/* Positional and relative uncertainty of adjusted stations (dynadjust_amd/csrc/uncertainty.h: the math, the conventions and the SP1
+ * 95 % figures).  Replace the reference's PU computation in its .apu printer (DynAdjustPrinter::PrintPositionalUncertainty), and here
+ * DynAdjustPrinter::StationResults, which downloads the whole packed variance matrix of every block to read its 3x3 diagonal blocks:
+ * these read only the blocks they need from `variances` (the block's rigorous variances, order 3 * stations of the block, lower triangle)
+ * where it sits in HBM, one launch per call.
+ *   station: local_stn[k] (block-local station) with the geodetic frame latlon[2k], latlon[2k+1] (radians) -> out[k]
+ *   pair:    local_pairs[2k], local_pairs[2k+1] = (i, j): D = C_ii + C_jj - C_ij - C_ij^T, the covariance of the vector i -> j, reduced in
+ *            the local frame latlon_first[2k], latlon_first[2k+1] of the pair's FIRST station; i == j gives zeros
+ * Every index is checked against the block's station count before anything runs on the device (DNAGPU_EINVAL).  Host buffers;
+ * the call returns when `out` is filled. */
+typedef struct {
+    double enu[6];             /* local covariance ee en eu nn nu uu (m^2) */
+    double semi_major, semi_minor, azimuth;   /* 1-sigma horizontal error ellipse (m, m, radians clockwise from north in [0, pi)) */
+    double hz_pu, vt_pu;       /* horizontal and vertical positional uncertainty at 95 % (m) */
+} dnagpu_uncertainty;
+int dnagpu_block_station_uncertainty(dnagpu_ctx* ctx, int chain, uint32_t blk, const dnagpu_matrix* variances, const uint32_t* local_stn,
+                                     const double* latlon, uint32_t count, dnagpu_uncertainty* out);
+int dnagpu_block_pair_uncertainty(dnagpu_ctx* ctx, int chain, uint32_t blk, const dnagpu_matrix* variances, const uint32_t* local_pairs,
+                                  const double* latlon_first, uint32_t count, dnagpu_uncertainty* out);
+/* host only, no device: the same math on one 3x3 (cxyz = xx xy xz yy yz zz), for tests */
+void dnagpu_debug_uncertainty_3x3(const double cxyz[6], double lat, double lon, dnagpu_uncertainty* out);
+
 /* m <- sum_i A_i^T W_i A_i (measurement contributions only, CML order) */
 int dnagpu_form_normals(dnagpu_ctx* ctx, int chain, uint32_t blk, dnagpu_matrix* m);
 /* m[3s..3s+2, 3s..3s+2] += sign * w9 (column-major 3x3) for k stations */
